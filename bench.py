@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- CG iterations/s and GEMV GB/s of the MI355X-native dense CG hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run measures the headline only: set-up (matrix generation, settling launches), W warm-up steps, K timed steps,
+the self-check, one JSON line.  Everything else described below -- the side sizes ("also"), "config4_gemv", the symmetric
+option, the CPU baseline, the live PMC traffic passes, the clock/power sampler, the cold-start figure, and for N > 1 the
+comparison exchanges and the child-process legs of the other topology -- runs only with --full.
+--dump-outputs DIR writes what the timed path returned after its last step (the solution x and the recursive relative
+residual, float64 .npy files) into DIR; the inputs are seeded, so two builds can be compared output for output.
 
 A "step" is ONE Conjugate-Gradient iteration (row-sharded GEMV Ap=A.p + the two dot products +
 the x, r, p updates + the per-iteration exchange) on a synthetic dense SPD system that is already
@@ -11,12 +18,12 @@ resident in HBM when the timed region starts.  Workload for every GPU count: BAS
 configs[2], N=65536 fp64 (34.4 GB, fits one MI355X) -- strong scaling, so the driver's 1/2/4/8
 series is one problem.  The matrix is the device-generated random dense SPD system
 (lam_hip_generate_random_spd, cond=1e6 so CG is still iterating at the end of the run).
-At N=1 GPU the line also carries, under "also", configs[1] (N=32768) and the sizes the reference
+With --full, at N=1 GPU the line also carries, under "also", configs[1] (N=32768) and the sizes the reference
 published numbers for (N=10000/20000/40000, TESTS/BEST_RESULTS:362-372) with the per-iteration cost
 outside the GEMV ("other_us"); they run after the headline in the same process and context.  Under
 "config4_gemv": BASELINE configs[3], the N=131072 fp32 / bf16-storage GEMV (VALU kernel and MFMA variant).
 
-N > 1 GPUs: ONE command measures BOTH multi-GPU topologies the product has, whichever way it is started.
+N > 1 GPUs, with --full: ONE command measures BOTH multi-GPU topologies the product has, whichever way it is started.
   * started by a launcher (RANK / WORLD_SIZE in the environment: the driver's torchrun line): the HEADLINE is the rank mode --
     one process per GPU, the exchange is RCCL inside liblam_hip.so, the ranks find each other through the package's own socket
     rendezvous (no torch in the process) -- and rank 0 also runs the one-process topology in a child process
@@ -41,8 +48,8 @@ the headline ("headline_from", "own_topology_error"; exit code 4), or -- with no
 One JSON line is printed by rank 0.  `roofline` is for the dominant kernel (its name comes from the
 library): achieved = algorithmic bytes of one launch / its average duration measured with HIP events on
 the launch stream inside the timed steps; `roofline.traffic` = HBM bytes per launch from two short rocprofv3
-PMC passes run as child processes at the start (N=1; otherwise the committed profile's value, tagged).
-`cpu_baseline` (rank 0, N=1 only) times the reference's
+PMC passes run as child processes at the start (N=1 with --full; otherwise the committed profile's value, tagged).
+`cpu_baseline` (rank 0, N=1 only, --full) times the reference's
 own CPU driver (oracle/_ref, built from /root/reference in the build container) -- or, if that
 binary is missing, the oracle port -- on a bounded sample.
 """
@@ -179,7 +186,7 @@ def run_mfma_child(n4):
         return None
 
 
-def run_config(s, n, warmup, steps, barrier, seed=1234, cond=1e6, symmetric=False, generate=True, ramp_s=0.0):
+def run_config(s, n, warmup, steps, barrier, seed=1234, cond=1e6, symmetric=False, generate=True, ramp_s=0.0, measure_cold=False):
     """W untimed + K timed CG iterations on solver `s`.  The context keeps its matrix allocation when N
     shrinks (grow-only), so several configurations can follow each other in one process without a large
     hipFree in between ("allocation history")."""
@@ -191,19 +198,22 @@ def run_config(s, n, warmup, steps, barrier, seed=1234, cond=1e6, symmetric=Fals
         raise RuntimeError("option 'symmetric' is not available for this configuration")
     cold = None
     if ramp_s > 0:
-        # for the record: the same W + K steps measured WITHOUT the ramp, i.e. what round 2's bench measured (the device's
-        # first ~0.3 s of load after idling); reported next to the headline as "cold_start", never as `value`
-        s.cg_init()
-        if warmup > 0:
-            s.cg_iterate(warmup, 0.0)
-        barrier()
-        t0c = time.perf_counter()
-        st_c = s.cg_iterate(steps, 0.0)
-        barrier()
-        cold = {"value": steps / (time.perf_counter() - t0c), "gemv_ms": st_c["t_gemv"] * 1e3,
-                "what": "the same warm-up + timed steps right after the matrix generation, before the settling launches "
-                        "(inside the window in which the driver still wipes the VRAM the child processes released)"}
-        cold["settled_for_s"] = settle(s, ramp_s)
+        s.cg_init()                              # p = b: a real vector in the GEMV's p replica for the settling launches
+        if measure_cold:
+            # for the record (--full): the same W + K steps measured WITHOUT the ramp, i.e. what round 2's bench measured (the
+            # device's first ~0.3 s of load after idling); reported next to the headline as "cold_start", never as `value`
+            if warmup > 0:
+                s.cg_iterate(warmup, 0.0)
+            barrier()
+            t0c = time.perf_counter()
+            st_c = s.cg_iterate(steps, 0.0)
+            barrier()
+            cold = {"value": steps / (time.perf_counter() - t0c), "gemv_ms": st_c["t_gemv"] * 1e3,
+                    "what": "the same warm-up + timed steps right after the matrix generation, before the settling launches "
+                            "(inside the window in which the driver still wipes the VRAM the child processes released)"}
+        settled_s = settle(s, ramp_s)
+        if cold is not None:
+            cold["settled_for_s"] = settled_s
     run_config.cold = cold
     s.cg_init()
     if warmup > 0:
@@ -214,6 +224,15 @@ def run_config(s, n, warmup, steps, barrier, seed=1234, cond=1e6, symmetric=Fals
     barrier()
     dt = time.perf_counter() - t0
     return st, dt
+
+
+def dump_outputs(out_dir, x, st):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the solution x (lam_hip_get_solution)
+    and the recursive relative residual of the returned stats -- as float64 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), np.asarray(x, dtype=np.float64))
+    np.save(os.path.join(out_dir, "rel_residual.npy"), np.array([st["rel_err"]], dtype=np.float64))
 
 
 def measure_traffic(n):
@@ -362,7 +381,7 @@ def maybe_die(leg, where):
 
 def leg_command(args, leg, out_path):
     return [sys.executable, os.path.abspath(__file__), "--leg", leg, "--leg-out", out_path, "--gpus", str(max(1, args.gpus)), "--steps", str(args.steps),
-            "--warmup", str(args.warmup), "--order", str(args.n), "--gemv-timing", str(args.gemv_timing)]
+            "--warmup", str(args.warmup), "--order", str(args.n), "--gemv-timing", str(args.gemv_timing), "--full"]     # legs run only with --full
 
 
 def run_leg(args, leg, nprocs, timeout, rank_env=None, rdzv_file=None, expect_record=True):
@@ -590,12 +609,17 @@ def rank_mode_measure(lam, args, rdzv, part, leg_name=None, on_headline=None):
                "parallelism": f"row-sharded x{world}, 1 process/GPU, {what}"}
         if part == "main":
             host_ns0 = s.get_option("host_enqueue_ns")
-            st, dt = run_config(s, n, args.warmup, args.steps, barrier, ramp_s=args.ramp if leg_name is None else min(args.ramp, 0.3))
+            st, dt = run_config(s, n, args.warmup, args.steps, barrier, ramp_s=args.ramp if leg_name is None else min(args.ramp, 0.3),
+                                measure_cold=args.full)
             maybe_die(leg_name, "main")
             rec["kernel"] = s.gemv_kernel_name()
             rec["cold_start"] = run_config.cold
             rec["exchange_effective"] = s.get_option("exchange_effective")
-            rec["host_enqueue_us_per_step"] = (s.get_option("host_enqueue_ns") - host_ns0) * 1e-3 / ((args.warmup + args.steps) * (2 if args.ramp > 0 else 1))
+            rec["host_enqueue_us_per_step"] = (s.get_option("host_enqueue_ns") - host_ns0) * 1e-3 / ((args.warmup + args.steps) * (2 if run_config.cold else 1))
+            if args.dump_outputs and leg_name is None:
+                x = s.solution()               # a collective in the rank mode: every rank takes part, rank 0 writes
+                if rank == 0:
+                    dump_outputs(args.dump_outputs, x, st)
             dt, st = max_over_ranks(dt, st)
             true_res = s.true_residual()
             check, failures = self_check(lam, args, world, st, true_res, rank, rdzv)
@@ -622,9 +646,9 @@ def rank_mode_measure(lam, args, rdzv, part, leg_name=None, on_headline=None):
                 dt_, st_ = max_over_ranks(time.perf_counter() - t0_, st_)
                 modes[label] = mode_record(args.steps, dt_, st_, s.true_residual())
 
-            if world > 1 or os.environ.get("LAM_HIP_FORCE_RCCL", "0") not in ("", "0"):
+            if args.full and (world > 1 or os.environ.get("LAM_HIP_FORCE_RCCL", "0") not in ("", "0")):
                 # Same problem, same context, the other exchanges of the rank mode (all product paths under the same parity
-                # tests) -- recorded for comparison, never the headline.
+                # tests) -- recorded for comparison (--full), never the headline.
                 if default_exchange != 0:
                     timed("allgather_x2+allgather_p", exchange=0, overlap=1)
                 timed("allgather_x2+allgather_p, no overlap", exchange=0, overlap=0)
@@ -731,15 +755,18 @@ def one_process_measure(lam, args, n_gpus, part, leg_name=None, on_headline=None
 
         if part == "main":
             host_ns0 = s.get_option("host_enqueue_ns")
-            st, dt = run_config(s, n, args.warmup, args.steps, nobarrier, ramp_s=args.ramp if leg_name is None else min(args.ramp, 0.3))
+            st, dt = run_config(s, n, args.warmup, args.steps, nobarrier, ramp_s=args.ramp if leg_name is None else min(args.ramp, 0.3),
+                                measure_cold=args.full)
             rec["kernel"] = s.gemv_kernel_name()
             rec["cold_start"] = run_config.cold
             gemv_fastest = s.get_option("gemv_ns_min_shard") * 1e-6      # ms; st["t_gemv"] is the slowest shard's: the skew between them
             rec["gemv_ms_fastest_shard"] = gemv_fastest
             effective = s.get_option("exchange_effective")
             rec["exchange_effective"] = effective
-            host_us = (s.get_option("host_enqueue_ns") - host_ns0) * 1e-3 / ((args.warmup + args.steps) * (2 if args.ramp > 0 else 1))
+            host_us = (s.get_option("host_enqueue_ns") - host_ns0) * 1e-3 / ((args.warmup + args.steps) * (2 if run_config.cold else 1))
             rec["host_enqueue_us_per_step"] = host_us
+            if args.dump_outputs and leg_name is None:
+                dump_outputs(args.dump_outputs, s.solution(), st)
             true_res = s.true_residual()
             check, failures = self_check(lam, args, n_gpus, st, true_res, 0, None)
             rec.update(dt=dt, st=st, true_res=true_res, self_check=check, failures=failures)
@@ -759,6 +786,8 @@ def one_process_measure(lam, args, n_gpus, part, leg_name=None, on_headline=None
             if on_headline is not None:
                 on_headline(copy.deepcopy(rec))
             maybe_fail_main(leg_name, "late")
+            if not args.full:                  # the comparison exchanges below run with --full only
+                return rec
             timed_local = make_timed_local(s, args, modes, vs_ref)
             timed_local(LOCAL_LABELS[1] + ", join through shard 0", exchange=1, exchange_join=1)
             timed_local(LOCAL_LABELS[1] + ", all-to-all join", exchange=1, exchange_join=0)
@@ -935,8 +964,9 @@ def main():
                     "comes from profiles/traffic.json, tagged as such)")
     ap.add_argument("--no-legs", action="store_true", help="N > 1: do not start the child-process legs (the other topology, the experimental exchange)")
     ap.add_argument("--gemv-timing", type=int, default=4, help="time the GEMV (and the exchange) of every T-th iteration with HIP-event pairs")
-    ap.add_argument("--ramp", type=float, default=0.6, help="seconds of untimed GEMV launches before the warm-up steps of the headline "
-                    "(waits out the driver's wipe of VRAM released by the child processes, see settle); 0 = none")
+    ap.add_argument("--ramp", type=float, default=None, help="seconds of untimed GEMV launches before the warm-up steps of the headline "
+                    "(waits out the driver's wipe of VRAM released by the child processes, see settle); 0 = none; default 0.6 with "
+                    "--full or under a profiler, else 5")
     ap.add_argument("--config4-n", type=int, default=131072, help="matrix order of the configs[3] GEMV-only side run")
     ap.add_argument("--cpu-sample-n", type=int, default=0, help="matrix order of the CPU baseline sample (0 = the workload's own N: "
                     "no extrapolation; the reference driver needs 8*N^2 bytes of host memory)")
@@ -944,10 +974,19 @@ def main():
     ap.add_argument("--leg-timeout", type=float, default=120.0, help="seconds a child-process leg may take (a healthy one needs 10-40 s at N=65536)")
     ap.add_argument("--headline-timeout", type=float, default=240.0, help="N > 1: seconds this process's own topology may take before rank 0 "
                     "prints the line without it (a healthy one needs 20-60 s at N=65536)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: side sizes, configs[3], the symmetric "
+                    "option, the CPU baseline, the live PMC traffic passes, the clock/power sampler, the cold-start figure; N > 1: the "
+                    "comparison exchanges and the child-process legs of the other topology")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned after its last step "
+                    "(solution x, recursive relative residual) as float64 .npy files into DIR")
     ap.add_argument("--mfma-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--leg-out", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.ramp is None:
+        # a plain run starts no child processes in front of its headline, so nothing else waits out the driver's wipe of the VRAM
+        # that the PREVIOUS benchmark process released (34 GB after a plain run, 137 GB after a --full one): its settling lasts longer
+        args.ramp = 0.6 if args.full or args.leg or under_profiler() else 5.0
     if args.mfma_child:
         return mfma_child(args.config4_n)
     if args.leg:
@@ -980,24 +1019,25 @@ def main():
     # Children go FIRST: nothing has touched the GPU yet (a process that has initialised the GPU must not fork+exec on this
     # pool), and never under a profiler (its tool library initialises the GPU before main()).
     cb, mfma_rows = None, None
-    if solo and not args.no_also and not profiled and not args.symmetric:
+    side = solo and args.full and not profiled           # a plain run measures the headline only
+    if side and not args.no_also and not args.symmetric:
         mfma_rows = run_mfma_child(args.config4_n)      # first: its 34 GB are wiped while the CPU baseline runs
-    if solo and not args.no_cpu_baseline and not profiled:
+    if side and not args.no_cpu_baseline:
         cb = cpu_baseline(args.cpu_sample_n or args.n, args.cpu_sample_iters)
     live_traffic = (None, None)
-    if solo and not args.no_traffic and not profiled and not args.symmetric:
+    if side and not args.no_traffic and not args.symmetric:
         live_traffic = measure_traffic(args.n)
         if live_traffic[0] is None:
             sys.stderr.write(f"[bench] live PMC traffic measurement not available: {live_traffic[1]}\n")
 
-    sampler = DeviceStateSampler() if solo and not profiled and os.environ.get("LAM_BENCH_NO_SAMPLER", "0") in ("", "0") else None
+    sampler = DeviceStateSampler() if side and os.environ.get("LAM_BENCH_NO_SAMPLER", "0") in ("", "0") else None
     t_window0 = time.time()
 
     # N > 1: the legs (see the module docstring).  `other` = the topology this process is NOT; `direct_*` = the EXPERIMENTAL
     # exchange of either topology, each in processes of its own.
     legs = {}
     forced_rccl = use_dist and os.environ.get("LAM_HIP_FORCE_RCCL", "0") not in ("", "0")     # a 1-rank communicator (tests on one GPU)
-    want_legs = (n_gpus > 1 or forced_rccl) and not args.no_legs and not profiled and not args.symmetric
+    want_legs = args.full and (n_gpus > 1 or forced_rccl) and not args.no_legs and not profiled and not args.symmetric
     want_direct = want_legs and os.environ.get("LAM_BENCH_DIRECT", "1") != "0"
     if want_legs and not use_dist:
         def rank_env(i):
@@ -1078,12 +1118,14 @@ def main():
 
         def barrier():
             pass
-        st, dt = run_config(s, n, args.warmup, args.steps, barrier, symmetric=args.symmetric, ramp_s=args.ramp)
+        st, dt = run_config(s, n, args.warmup, args.steps, barrier, symmetric=args.symmetric, ramp_s=args.ramp, measure_cold=args.full)
         kernel_name = s.gemv_kernel_name()
         cold_start = run_config.cold
         parallelism = "1 GPU"
         # host time the library spent issuing one iteration of the headline configuration (its waits for the device excluded)
-        host_us_per_step = (s.get_option("host_enqueue_ns") - host_ns0) * 1e-3 / ((args.warmup + args.steps) * (2 if args.ramp > 0 else 1))
+        host_us_per_step = (s.get_option("host_enqueue_ns") - host_ns0) * 1e-3 / ((args.warmup + args.steps) * (2 if cold_start else 1))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, s.solution(), st)
         device_state = sampler.summary(t_window0, time.time()) if sampler is not None else None
         true_res = s.true_residual()
         check, failures = self_check(lam, args, 1, st, true_res, 0, None, symmetric=args.symmetric)
@@ -1106,12 +1148,12 @@ def main():
         merge_direct(exchange_modes, legs.get("one_direct" if use_dist else "rank_direct"), true_res)
         other_topology = {"error": own_error}
 
-    # Side measurements, same process, same context, AFTER the headline (N=1 only, not under a profiler):
+    # Side measurements (--full), same process, same context, AFTER the headline (N=1 only, not under a profiler):
     # the opt-in symmetric product on the same system, then configs[1] (N=32768) and the sizes the reference
     # published numbers for (TESTS/BEST_RESULTS:362-372), largest first so the matrix allocation is re-used.
     also, sym = None, None
     keep_alive = []
-    if solo and not args.no_also and not profiled and not args.symmetric:
+    if side and not args.no_also and not args.symmetric:
         def barrier():
             pass
         try:
@@ -1153,7 +1195,7 @@ def main():
     # kernel of each dtype and, for bf16, the MFMA-fed variant beside it (kept as an option: it is slower).  Own
     # contexts, after the fp64 context has been closed; yardstick is still HBM GB/s (GEMV has no contraction for MFMA).
     config4 = None
-    if solo and not args.no_also and not profiled and not args.symmetric:
+    if side and not args.no_also and not args.symmetric:
         config4 = []
         n4 = args.config4_n
         # NO context is closed before the last timed region: the driver wipes released VRAM in the background, and a
@@ -1219,8 +1261,10 @@ def main():
                                f"SPD matrix (cond 1e6) + random rhs, {args.steps} fixed iterations",
                    "n": n, "parallelism": parallelism,
                    "untimed_setup": f"matrix generated on the device; {args.ramp} s of GEMV launches before the warm-up steps (waits out "
-                                    "the driver's background wipe of the VRAM the child processes released: profiles/r04_bf16_gap_probe.txt; "
-                                    "`value_cold` is the same measurement without it -- rounds 1-2 and BASELINE-style figures are cold)",
+                                    "the driver's background wipe of the VRAM the child processes or an earlier process released: "
+                                    "profiles/r04_bf16_gap_probe.txt"
+                                    + ("; `value_cold` is the same measurement without it -- rounds 1-2 and BASELINE-style figures are cold)"
+                                       if cold_start else ")"),
                    "matrix_bytes_per_gpu": 8.0 * n * n / n_gpus, **({"shard_devices": shard_devices} if shard_devices else {})},
         "gemv_ms": st["t_gemv"] * 1e3,
         **({"exchange_us": st["t_exchange"] * 1e6, "gemv_plus_comm_ms": (st["t_gemv"] + st["t_exchange"]) * 1e3} if n_gpus > 1 or use_dist else {}),
@@ -1251,7 +1295,7 @@ def main():
         # the topology the headline is not: measured by child processes in front of the headline (None: legs were switched off) --
         # or, when the headline had to come from that leg, this process's own topology with the reason it failed
         key = "one_process_topology" if use_dist != (headline_from is not None) else "rank_mode_rccl"
-        out[key] = other_topology if other_topology is not None else ({"skipped": "--no-legs, a profiler, or --symmetric"} if not want_legs else {"error": "leg not run"})
+        out[key] = other_topology if other_topology is not None else ({"skipped": "no --full, --no-legs, a profiler, or --symmetric"} if not want_legs else {"error": "leg not run"})
     if headline_from is not None:
         out["headline_from"], out["own_topology_error"] = headline_from, own_error
     if comparison_error is not None:

@@ -347,7 +347,7 @@ def _bench_torchrun(mock, nproc, tmp_path, extra_env=None):
     port = 29700 + nproc + os.getpid() % 100
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "20",
-           "--warmup", "3", "--order", "8192"]
+           "--warmup", "3", "--order", "8192", "--full"]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
 
 
@@ -456,7 +456,7 @@ def test_bench_stdout_is_one_json_line_with_real_rccl(tmp_path):
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LD_PRELOAD", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(29800 + os.getpid() % 100), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10",
-           "--warmup", "2", "--order", "8192"]
+           "--warmup", "2", "--order", "8192", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -477,7 +477,7 @@ def test_bench_one_process_topology_records_every_exchange(mock_async, tmp_path,
     the headline is the library default (gather-Ap).  All shards on GPU 0 here (LAM_BENCH_DEVICE_IDS), one hardware
     queue per stream so that kernels of one shard can wait for kernels of another."""
     env = _one_process_env(mock_async, gpus)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "3", "--order", "8192"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "3", "--order", "8192", "--full"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -527,7 +527,7 @@ def test_bench_headline_survives_a_dying_leg(mock_async, tmp_path, victim):
     whole rank-mode leg."""
     gpus = 2
     env = _one_process_env(mock_async, gpus, LAM_BENCH_KILL_LEG=victim)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "3", "--order", "8192", "--leg-timeout", "90"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "3", "--order", "8192", "--leg-timeout", "90", "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -558,7 +558,7 @@ def test_bench_line_survives_its_own_topology(mock_async, tmp_path, how, expect_
     gpus = 2
     env = _one_process_env(mock_async, gpus, LAM_BENCH_FAIL_MAIN=how, LAM_BENCH_DIRECT="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "3", "--order", "8192",
-                        "--leg-timeout", "90", "--headline-timeout", "8"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--leg-timeout", "90", "--headline-timeout", "8", "--full"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == (4 if expect_from == "leg" else 0), r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[:2000]
