@@ -41,6 +41,8 @@ namespace lam {
 
 constexpr int kBlock = 256;          // 4 waves of 64
 constexpr int kWaves = kBlock / 64;
+// 16 zero bytes: what the GEMV lanes past the end of a ragged tile load in place of matrix elements (zero in every element type)
+__device__ __attribute__((aligned(16))) const unsigned int kZeroVec16[4] = {0u, 0u, 0u, 0u};
 constexpr int kMaxShards = 64;         // shards of one process / ranks of one communicator (the reference's largest published run: 64 GPUs)
 constexpr size_t kAgreeBytes = 256 * (size_t)kMaxShards;   // device scratch of the small set-up collectives: one 256-byte record per rank
 
@@ -551,20 +553,20 @@ gemv_tile_kernel(GemvArgs<TA, TV> a)
         } else {
             // Ragged last tile of a segment (N not a multiple of TILE: 18 % of the columns at N=10000): the SAME
             // streaming body over ceil(cols / STEP) steps.  Lanes past the end of the segment read the row's last
-            // vector again (address clamped: in bounds) against a ZERO of p -- the p tile is zero-filled behind `cols`
-            // (LDS) or the product is masked (p from L2) -- so they add +-0 and the sums keep their bits.  No second
+            // vector again (address clamped: in bounds) and multiply a ZERO in its place (and a zero of p: the p tile is
+            // zero-filled behind `cols` (LDS) or masked (p from L2)), so they add exactly +0 -- also when that last vector
+            // holds +-Inf or NaN, which times the zero of p alone would turn into a NaN row sum.  No second
             // code path with its own registers: round 2's separately unrolled ragged body doubled the kernels' VGPRs
             // (fp32 54 -> 98, bf16 104 -> 256: occupancy 8 -> 4 and 4 -> 1) and the full-tile path paid for it.
             const int nsteps = (int)((cols + STEP - 1) / STEP);
-            const uint32_t last = cols - VEC;                 // cols is a multiple of VEC (>= VEC)
 #pragma unroll UNROLL
             for (int s = 0; s < nsteps; s++) {
                 const uint32_t col = (uint32_t)s * STEP + (uint32_t)lane * VEC;
-                const uint32_t colc = col < last ? col : last;
                 avec_t av[R];
 #pragma unroll
                 for (int r = 0; r < R; r++) {
-                    const avec_t *src = reinterpret_cast<const avec_t *>(rowp[r] - (uint64_t)lane * VEC + c0 + colc);
+                    const avec_t *src = col < cols ? reinterpret_cast<const avec_t *>(rowp[r] + c0 + (uint64_t)s * STEP)
+                                                   : reinterpret_cast<const avec_t *>(kZeroVec16);
                     av[r] = NT ? __builtin_nontemporal_load(src) : *src;
                 }
                 TV pv[VEC];
@@ -687,18 +689,18 @@ gemv_coop_kernel(GemvArgs<TA, TV> a)
             }
         } else {
             // ragged last tile of a segment: the same streaming body over ceil(cols / super-step) super-steps; lanes past
-            // the end re-read the row's last vector (clamped address) against the zeros the staging put behind `cols`,
-            // so they add +-0 (see gemv_tile_kernel: no second unrolled body, no second set of registers)
+            // the end re-read the row's last vector (clamped address) and multiply a zero in its place with the zeros the
+            // staging put behind `cols`, so they add exactly +0, a non-finite last vector included (see gemv_tile_kernel:
+            // no second unrolled body, no second set of registers)
             const int nsteps = (int)((cols + STEP * WAVES - 1) / (STEP * WAVES));
-            const uint32_t last = cols - VEC;
 #pragma unroll UNROLL
             for (int s = 0; s < nsteps; s++) {
                 const uint32_t col = (uint32_t)s * (STEP * WAVES) + woff;
-                const uint32_t colc = col < last ? col : last;
                 avec_t av[R];
 #pragma unroll
                 for (int r = 0; r < R; r++) {
-                    const avec_t *src = reinterpret_cast<const avec_t *>(rowp[r] - woff + c0 + colc);
+                    const avec_t *src = col < cols ? reinterpret_cast<const avec_t *>(rowp[r] + c0 + (uint64_t)s * (STEP * WAVES))
+                                                   : reinterpret_cast<const avec_t *>(kZeroVec16);
                     av[r] = NT ? __builtin_nontemporal_load(src) : *src;
                 }
                 TV pv[VEC];
@@ -780,15 +782,14 @@ __device__ __forceinline__ void coop_stream_tile(const TA *const (&rowp)[R], uin
         }
     } else {
         const int nsteps = (int)((cols + STEP * WAVES - 1) / (STEP * WAVES));
-        const uint32_t last = cols - VEC;
 #pragma unroll UNROLL
         for (int s = 0; s < nsteps; s++) {
             const uint32_t col = (uint32_t)s * (STEP * WAVES) + woff;
-            const uint32_t colc = col < last ? col : last;
             avec_t av[R];
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                const avec_t *src = reinterpret_cast<const avec_t *>(rowp[r] - woff + c0 + colc);
+                const avec_t *src = col < cols ? reinterpret_cast<const avec_t *>(rowp[r] + c0 + (uint64_t)s * (STEP * WAVES))
+                                               : reinterpret_cast<const avec_t *>(kZeroVec16);
                 av[r] = NT ? __builtin_nontemporal_load(src) : *src;
             }
             TV pv[VEC];

@@ -104,8 +104,50 @@ def persistent(dtype_name, n):
     assert res[0] == res[1] == res[2] == res[3]
 
 
+def exact_gemv(dtype_name, n):
+    """Every other tile and cooperative-row shape of the tuning build on the dense integer matrix of tests/exact_data.py: y = A x
+    bit for bit (every partial sum is an exact integer), on one shard and on three."""
+    import exact_data as E
+    dt = getattr(lam, dtype_name)
+    x = E.int_vec(n, n + 1)
+    with lam.Solver(dt) as s1, lam.Solver(dt, device_ids=[0, 0, 0]) as s3:
+        for s in (s1, s3):
+            s.set_problem(n)
+        (y,) = E.generate(n, [s1.upload_rows, s3.upload_rows], [x])
+        want = y.astype(s1.vec_dtype)
+        for s in (s1, s3):
+            for v in (1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 14, 15, 16, 18, 25, 26, 27):
+                s.set_option("gemv_variant", v)
+                got = s.gemv(x)
+                bad = np.flatnonzero(got != want)
+                assert bad.size == 0, (dtype_name, n, s.num_shards(), v, s.gemv_kernel_name(), bad[:6])
+
+
+def exact_first_step(dtype_name, n):
+    """The persistent launch's first CG step on the integer system: x1 = fl(alpha_TV b) bit for bit (tests/test_gpu_exact.py)."""
+    import exact_data as E
+    dt = getattr(lam, dtype_name)
+    b = E.int_vec(n, 12)
+    with lam.Solver(dt) as s:
+        s.set_problem(n)
+        (Ab,) = E.generate(n, [s.upload_rows], [b])
+        s.set_rhs(b)
+        s.set_option("gemv_variant", 10)
+        s.set_option("persistent", 1)
+        alpha, x1, bb, pAp, r1 = E.first_cg_step(b, Ab, s.vec_dtype)
+        x1 = x1 + s.vec_dtype(0)
+        s.solve(1, 1e-30)
+        assert s.get_option("persistent_effective") == 1
+        assert s.stats["num_iters"] == 2                     # max_iters + 1, as the reference reports it
+        x = s.solution()
+        assert np.array_equal(x.view(np.uint8), x1.view(np.uint8)), (alpha, bb, pAp)
+        re_host, bound = E.rel_err_bound(b, Ab, alpha, r1, bb, 2.0 ** -53 if dtype_name == "F64" else 2.0 ** -24)
+        assert abs(s.stats["rel_err"] - re_host) <= bound, (s.stats["rel_err"], re_host, bound)
+
+
 CASES = {"mfma": (mfma, (int, int)), "launch_chain": (launch_chain, (str, int, int)), "host_enqueue": (host_enqueue, (int, int)),
-         "persistent": (persistent, (str, int))}
+         "persistent": (persistent, (str, int)), "exact_gemv": (exact_gemv, (str, int)),
+         "exact_first_step": (exact_first_step, (str, int))}
 
 
 def main():
