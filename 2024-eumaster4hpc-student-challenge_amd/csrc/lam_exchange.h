@@ -35,9 +35,11 @@ int64_t symmetric_from_env(int64_t dflt)
     return (k >= 0 && k <= 2) ? k : dflt;
 }
 
-// max |A - A^T| and max |A| of the matrix a single-PROCESS context holds (one tiled pass over the upper triangle and its mirror
-// image; with several shards shard 0's device reads the other shards' rows through peer access)
-int measure_asymmetry(lam_hip_ctx *c, double *max_asym, double *max_abs)
+// max |A - A^T| and max |A| (over the finite elements) of the matrix a single-PROCESS context holds, and `beyond`: the largest
+// |A_ij - A_ji| among the pairs further apart than rel * max(|A_ij|, |A_ji|) -- see asymmetry_kernel for the three figures and for
+// how non-finite elements count (a pair the triangles disagree on with a NaN or an Inf in it: +Inf).  One tiled pass over the upper
+// triangle and its mirror image; with several shards shard 0's device reads the other shards' rows through peer access.
+int measure_asymmetry(lam_hip_ctx *c, double rel, double *max_asym, double *max_abs, double *beyond)
 {
     return dispatch(c, [&](auto impl) -> int {
         using TA = typename ImplTraits<decltype(impl)>::TA;
@@ -52,29 +54,38 @@ int measure_asymmetry(lam_hip_ctx *c, double *max_asym, double *max_abs)
         for (int q = 0; q < shards.n; q++) shards.p[q] = c->sh[q].A;
         const int grid = 2048;
         DevBuf outb;
-        HIPCHK(c, hipMalloc(&outb.p, sizeof(double) * 2 * grid));
-        std::vector<double> h(2 * grid);
-        hipLaunchKernelGGL((asymmetry_kernel<TA>), dim3(grid), dim3(kBlock), 0, s.stream, shards, c->n / (uint64_t)c->total_shards, c->lda, c->n, outb.as<double>());
+        HIPCHK(c, hipMalloc(&outb.p, sizeof(double) * 3 * grid));
+        std::vector<double> h(3 * grid);
+        hipLaunchKernelGGL((asymmetry_kernel<TA>), dim3(grid), dim3(kBlock), 0, s.stream, shards, c->n / (uint64_t)c->total_shards, c->lda, c->n, rel, outb.as<double>());
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h.data(), outb.p, sizeof(double) * 2 * grid, hipMemcpyDeviceToHost, s.stream));
+        HIPCHK(c, hipMemcpyAsync(h.data(), outb.p, sizeof(double) * 3 * grid, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipStreamSynchronize(s.stream));
-        double m = 0.0, a = 0.0;
-        for (int i = 0; i < grid; i++) { m = std::max(m, h[i]); a = std::max(a, h[grid + i]); }
+        double m = 0.0, a = 0.0, x = 0.0;            // the kernel writes no NaN
+        for (int i = 0; i < grid; i++) { m = std::max(m, h[i]); a = std::max(a, h[grid + i]); x = std::max(x, h[2 * grid + i]); }
         *max_asym = m;
         *max_abs = a;
+        *beyond = x;
         return 0;
     });
 }
 
 // Option "symmetric" asked for through the ENVIRONMENT (a driver that cannot call lam_hip_set_option or lam_hip_check_symmetry,
-// e.g. the reference's own driver sources compiled against these headers): the library vouches for the precondition itself.
+// e.g. the reference's own driver sources compiled against these headers): the library vouches for the precondition itself, at every
+// entry point that can run the symmetric product (lam_hip_cg_init / lam_hip_solve, lam_hip_gemv, lam_hip_gemv_only), once per matrix.
 //   * not effective (rank mode / several shards on an exchange other than gather-Ap): said once on stderr, the general GEMV runs;
 //   * one process (one shard or several): A is compared with its transpose once per matrix (one pass over A; the rows of other
-//     shards through peer access).  Equal bit for bit: nothing to say.
-//     Unequal at rounding level (<= 64 ulp of the largest element: a file written by a generator that rounds A_ij and A_ji
-//     separately, like the reference's MKL-based one): a warning -- the upper triangle then DEFINES the system that is solved.
-//     More: refused, the general GEMV runs (and says so);
+//     shards through peer access).  Every pair agrees (equal values; equal infinities and NaN on both sides included): nothing to say.
+//     Unequal at rounding level: a warning -- the upper triangle then DEFINES the system that is solved.  Rounding level is
+//       fp64 / fp32 storage:  max|A - A^T| <= 64 ulp of the largest finite element -- a file written by a generator that forms A_ij
+//         and A_ji by separate dot products, like the reference's MKL-based one: its absolute error scales with max|A|, not with
+//         the element;
+//       bf16 storage: that model does not apply -- the file is fp32 and each side is rounded to bf16 on upload, so two elements
+//         that agree to fp32 rounding hold the same bf16 value or neighbours.  Every pair must satisfy
+//         |A_ij - A_ji| <= max(2^-7 max(|A_ij|, |A_ji|), 64 * 2^-24 max|A|): one bf16 unit in the last place of the pair, or the
+//         fp32 rule for elements near zero.  (64 bf16 ulp of max|A| would be HALF the largest element.)
+//     More, or a NaN / an Inf on one side of a pair only: refused, the general GEMV runs (and says so);
 //   * rank mode: the transpose lives in other processes -- not checked, the caller vouches as with the option.
+// lam_hip_set_option("symmetric") ends all this for the context: from then on the caller vouches.
 int env_symmetric_check(lam_hip_ctx *c)
 {
     if (!c->symmetric_from_env || c->opt_symmetric == 0) return 0;
@@ -88,12 +99,14 @@ int env_symmetric_check(lam_hip_ctx *c)
     }
     if (!c->symv_active() && !c->symv_multi_active()) return 0;           // not asked for at this size
     if (c->rank_mode || c->sym_checked_gen == c->matrix_gen) return 0;     // rank mode: the transpose lives in other processes
-    double asym = 0.0, amax = 0.0;
-    LAMCHK(measure_asymmetry(c, &asym, &amax));
+    const bool bf16 = c->dtype == LAM_HIP_BF16;
+    const double rel = bf16 ? 0x1p-7 : 0.0;                                // per-pair term: one bf16 unit in the last place
+    const double eps = c->dtype == LAM_HIP_F64 ? 2.220446049250313e-16 : (c->dtype == LAM_HIP_F32 ? 1.1920929e-07 : 0x1p-24);
+    double asym = 0.0, amax = 0.0, beyond = 0.0;
+    LAMCHK(measure_asymmetry(c, rel, &asym, &amax, &beyond));
     c->sym_checked_gen = c->matrix_gen;
-    const double eps = c->dtype == LAM_HIP_F64 ? 2.220446049250313e-16 : (c->dtype == LAM_HIP_F32 ? 1.1920929e-07 : 7.8125e-03);
     if (asym == 0.0) return 0;
-    if (asym <= 64.0 * eps * amax) {
+    if (beyond <= 64.0 * eps * amax) {
         fprintf(stderr, "lam_hip: LAM_HIP_SYMMETRIC: max|A - A^T| = %.3e (max|A| = %.3e): equal to rounding only -- the upper triangle "
                         "defines the system that is solved\n", asym, amax);
         return 0;

@@ -804,6 +804,7 @@ int lam_hip_gemv(lam_hip_ctx *c, const void *x_host, void *y_host)
 {
     if (!c || !x_host || !y_host) return LAM_HIP_EINVAL;
     if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
+    LAMCHK(env_symmetric_check(c));     // LAM_HIP_SYMMETRIC: this may be the first product on this matrix (once per matrix)
     const size_t ev = c->esz_v();
     for (auto &s : c->sh) {
         LAMCHK(set_dev(c, s));
@@ -850,6 +851,7 @@ int lam_hip_gemv_only(lam_hip_ctx *c, int reps, double *sec)
 {
     if (!c || !sec || reps < 1) return LAM_HIP_EINVAL;
     if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
+    LAMCHK(env_symmetric_check(c));     // as lam_hip_gemv
     c->cg_ready = false;
     double worst = 0.0;
     LAMCHK(dispatch(c, [&](auto impl) -> int {
@@ -959,8 +961,8 @@ int lam_hip_check_symmetry(lam_hip_ctx *c, double *max_abs_asymmetry)
     if (!c || !max_abs_asymmetry) return LAM_HIP_EINVAL;
     if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
     if (c->rank_mode) return fail(c, LAM_HIP_EINVAL, "symmetry check needs the whole matrix in one process");
-    double max_abs = 0.0;
-    return measure_asymmetry(c, max_abs_asymmetry, &max_abs);
+    double max_abs = 0.0, beyond = 0.0;
+    return measure_asymmetry(c, 0.0, max_abs_asymmetry, &max_abs, &beyond);
 }
 
 int lam_hip_debug_symv_plan(uint64_t n, int shards, int dtype, uint64_t *bad_pairs, uint64_t *bad_interior, uint64_t *ntasks)
@@ -1110,7 +1112,13 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
         if (!strcmp(name, "persistent")) { c->opt_persistent = value; c->cg_ready = false; }
         else c->opt_persist_chunk = value;
     }
-    else if (!strcmp(name, "symmetric")) { c->opt_symmetric = value; c->cg_ready = false; }   // other kernels, other partial arrays
+    else if (!strcmp(name, "symmetric")) {
+        // the caller vouches for A = A^T from here on: the environment's check (and a refusal it made) no longer applies to this context
+        c->opt_symmetric = value;
+        c->symmetric_from_env = false;
+        c->sym_refused = false;
+        c->cg_ready = false;        // other kernels, other partial arrays
+    }
     else if (!strcmp(name, "gemv_timing")) c->opt_gemv_timing = value < 0 ? 0 : value;
     else if (!strcmp(name, "verify_direct")) c->opt_verify_direct = value;
     else if (!strcmp(name, "host_threads") || !strcmp(name, "exchange_hub")) {

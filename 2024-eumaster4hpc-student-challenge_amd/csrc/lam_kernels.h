@@ -1373,10 +1373,18 @@ symv_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart,
     }
 }
 
-// max |A[i][j] - A[j][i]| over the local matrix (single shard) and max |A[i][j]| over the same elements: per-workgroup maxima in
-// out[blockIdx.x] and out[gridDim.x + blockIdx.x].  32 x 32 tiles of the upper triangle through LDS, so that both the tile and its
-// mirror image are read along rows (one pass over the matrix at a useful fraction of the stream rate: this runs once per matrix when
-// a driver asks for the symmetric product through the environment, lam_exchange.h env_symmetric_check).
+// The asymmetry of the matrix one process holds, over every pair {A[i][j], A[j][i]}; three per-workgroup maxima, in out[blockIdx.x],
+// out[gridDim.x + blockIdx.x] and out[2 * gridDim.x + blockIdx.x]:
+//   [0] max |A[i][j] - A[j][i]|.  A pair the two triangles agree on (equal values, infinities of one sign, two NaNs, zeros of either
+//       sign) counts 0; a pair they disagree on with a non-finite member (NaN or Inf against anything else) counts +Inf, so that it
+//       can neither drop out of a maximum (every comparison with NaN is false) nor hide behind max |A| = Inf;
+//   [1] max |A[i][j]| over the FINITE elements (what a tolerance may be scaled by);
+//   [2] the largest |A[i][j] - A[j][i]| among the pairs that differ by more than `rel` * max(|A[i][j]|, |A[j][i]|) (finite members
+//       only), 0 if there is none: with rel = 2^-7 the pairs that are further apart than one bf16 unit in the last place of the pair;
+//       with rel = 0 the same as [0].  A per-pair rule  |d| <= max(rel * max(|u|, |l|), abs_tol)  is violated somewhere iff [2] > abs_tol.
+// 32 x 32 tiles of the upper triangle through LDS, so that both the tile and its mirror image are read along rows (one pass over the
+// matrix at a useful fraction of the stream rate: this runs once per matrix when a driver asks for the symmetric product through the
+// environment, lam_exchange.h env_symmetric_check).
 __device__ __forceinline__ double elem_as_double(double v) { return v; }
 __device__ __forceinline__ double elem_as_double(float v) { return (double)v; }
 __device__ __forceinline__ double elem_as_double(__hip_bfloat16 v) { return (double)__uint_as_float(((unsigned)*reinterpret_cast<const unsigned short *>(&v)) << 16); }
@@ -1384,7 +1392,7 @@ __device__ __forceinline__ double elem_as_double(__hip_bfloat16 v) { return (dou
 // partition), whose matrix the launching device reads through peer access -- one-off, at the speed of the links.
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
-asymmetry_kernel(PtrList shards, uint64_t base_rows, uint64_t lda, uint64_t n, double *__restrict__ out)
+asymmetry_kernel(PtrList shards, uint64_t base_rows, uint64_t lda, uint64_t n, double rel, double *__restrict__ out)
 {
     auto elem = [&](uint64_t i, uint64_t j) -> double {
         uint64_t q = shards.n > 1 ? i / base_rows : 0;
@@ -1393,8 +1401,9 @@ asymmetry_kernel(PtrList shards, uint64_t base_rows, uint64_t lda, uint64_t n, d
     };
     constexpr int TS = 32;
     __shared__ double s_up[TS][TS + 1], s_lo[TS][TS + 1];
-    __shared__ double s_max[2][kWaves];
-    double m = 0.0, a = 0.0;
+    __shared__ double s_max[3][kWaves];
+    const double inf = __longlong_as_double(0x7FF0000000000000ll);
+    double m = 0.0, a = 0.0, x = 0.0;
     const uint64_t nt = (n + TS - 1) / TS, ntiles = nt * (nt + 1) / 2;
     const int tx = threadIdx.x % TS, ty = threadIdx.x / TS;          // 32 x 8 threads: four row passes per tile
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -1413,24 +1422,33 @@ asymmetry_kernel(PtrList shards, uint64_t base_rows, uint64_t lda, uint64_t n, d
         __syncthreads();
         for (int r = ty; r < TS; r += kBlock / TS) {
             const double u = s_up[r][tx], l = s_lo[tx][r];             // A[bi*TS + r][bj*TS + tx] and A[bj*TS + tx][bi*TS + r]
-            const double d = fabs(u - l), v = fmax(fabs(u), fabs(l));
+            const double au = fabs(u), al = fabs(l);
+            const double fu = au < inf ? au : 0.0, fl = al < inf ? al : 0.0;       // Inf and NaN (the comparison is false): 0
+            const double v = fu > fl ? fu : fl;
+            const bool same = u == l || (u != u && l != l);
+            const double diff = fabs(u - l);
+            const double d = same ? 0.0 : (diff < inf ? diff : inf);               // a NaN difference counts as Inf
             m = d > m ? d : m;
             a = v > a ? v : a;
+            x = (d > rel * v && d > x) ? d : x;
         }
     }
+    // from here on no value is a NaN: plain comparisons keep the maxima
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(m, off, 64), q = __shfl_xor(a, off, 64);
+        const double o = __shfl_xor(m, off, 64), q = __shfl_xor(a, off, 64), e = __shfl_xor(x, off, 64);
         m = o > m ? o : m;
         a = q > a ? q : a;
+        x = e > x ? e : x;
     }
-    if ((threadIdx.x & 63) == 0) { s_max[0][threadIdx.x >> 6] = m; s_max[1][threadIdx.x >> 6] = a; }
+    if ((threadIdx.x & 63) == 0) { s_max[0][threadIdx.x >> 6] = m; s_max[1][threadIdx.x >> 6] = a; s_max[2][threadIdx.x >> 6] = x; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double t0 = s_max[0][0], t1 = s_max[1][0];
-        for (int w = 1; w < kWaves; w++) { t0 = s_max[0][w] > t0 ? s_max[0][w] : t0; t1 = s_max[1][w] > t1 ? s_max[1][w] : t1; }
-        out[blockIdx.x] = t0;
-        out[gridDim.x + blockIdx.x] = t1;
+        for (int k = 0; k < 3; k++) {
+            double t = s_max[k][0];
+            for (int w = 1; w < kWaves; w++) t = s_max[k][w] > t ? s_max[k][w] : t;
+            out[(size_t)k * gridDim.x + blockIdx.x] = t;
+        }
     }
 }
 

@@ -219,7 +219,10 @@ int lam_hip_axpby(lam_hip_ctx *ctx, double alpha, const void *x_host, double bet
                   uint64_t n);
 
 /* max |A[i][j] - A[j][i]| of the matrix held by a single-PROCESS context (one shard or several; every storage type): lets a
- * caller verify the precondition of option "symmetric".  No reference counterpart. */
+ * caller verify the precondition of option "symmetric".  Exact: the fp64 difference of the two stored values, no tolerance.
+ * Non-finite elements: a pair the two triangles agree on (infinities of one sign, NaN on both sides, zeros of either sign)
+ * counts 0; a pair they disagree on with a NaN or an Inf in it counts +Inf -- the result is then +Inf, never 0 and never NaN.
+ * No reference counterpart. */
 int lam_hip_check_symmetry(lam_hip_ctx *ctx, double *max_abs_asymmetry);
 
 /* Host-only check of the symmetric product's PLAN (no device needed, no context): builds the task lists of all `shards` row shards
@@ -273,9 +276,14 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *                   One shard: the upper triangle; several (exchange 1): cyclic half windows per row, each shard contributes
  *                   a full-length vector to the exchange.  1 = where it pays (from 192 MiB of matrix on), 2 = always, 0
  *                   (default) = the reference's general GEMV.  Same results to rounding.  "symmetric_effective" (get).
- *                   Environment LAM_HIP_SYMMETRIC = 1 | 2 (drivers): the library then checks A = A^T itself once per matrix
- *                   (one process; warns at rounding level, refuses beyond; rank mode: unchecked) and says on stderr when the
- *                   option is not effective (several shards / ranks on an exchange other than 1).
+ *                   Environment LAM_HIP_SYMMETRIC = 1 | 2 (drivers): the library then checks A = A^T itself once per matrix,
+ *                   at the first lam_hip_cg_init / lam_hip_solve / lam_hip_gemv / lam_hip_gemv_only on it (one process;
+ *                   warns at rounding level, refuses beyond and runs the general GEMV; rank mode: unchecked) and says on
+ *                   stderr when the option is not effective (several shards / ranks on an exchange other than 1).
+ *                   Rounding level: fp64 / fp32 storage max|A - A^T| <= 64 ulp of the largest finite element; bf16 storage,
+ *                   per pair, |A_ij - A_ji| <= max(2^-7 max(|A_ij|, |A_ji|), 64 * 2^-24 max|A|) (one bf16 ulp of the pair).
+ *                   A NaN or an Inf on one side of a pair only: refused.  Setting the option with lam_hip_set_option ends
+ *                   the environment's check for that context (and lifts a refusal): the caller vouches from then on.
  *   "fuse_update"   1 (default) = the x, r, p updates of an iteration are ONE launch (r.r handed over inside the launch):
  *                   2 launches per shard and iteration.  Used only when the whole grid of all shards / ranks on the device
  *                   is resident ("fuse_effective" tells; "assume_cus" overrides the CU count for tests).  Same bits.
