@@ -274,6 +274,24 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         return true;
     }
 
+    // Several right-hand sides on the matrix already held (lam_hip_solve_many: independent CG recurrences, one pass over the matrix
+    // per iteration; one shard, double / float).  B: nrhs vectors of get_num_cols() elements, vector j at B + j * cols; X (may be
+    // null): the solutions in the same layout; num_iters / converged / rel_err (may be null): nrhs entries each.  stats() then
+    // describes the batch.  Returns true iff every column converged.  No reference counterpart (its drivers are run once per rhs
+    // file).  Not virtual on purpose: a member of a class template is instantiated only where it is called, so programs that do
+    // not use it link against an ABI without the batched entry points.
+    bool solve_many(int nrhs, const FloatingType *B, FloatingType *X, int max_iters, FloatingType rel_error, int32_t *num_iters = nullptr,
+                    int32_t *converged = nullptr, double *rel_err = nullptr)
+    {
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        lam_hip_stats st;
+        if (lam_hip_solve_many(_ctx, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0) return report("solve_many");
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        return st.converged != 0;
+    }
+
     // rows held by this process (all of them in the single-process classes), like the reference getters
     size_t get_num_rows() const
     {

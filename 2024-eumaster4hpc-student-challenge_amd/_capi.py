@@ -16,6 +16,7 @@ TUNING_LIB = os.path.join(_HERE, "liblam_hip_tuning.so")
 
 F64, F32, BF16 = 0, 1, 2
 ABI_VERSION = 4     # include/lam_hip.h LAM_HIP_ABI_VERSION
+MAX_RHS = 8         # include/lam_hip.h LAM_HIP_MAX_RHS
 _VEC_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
 _HOST_MAT_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
 
@@ -33,6 +34,14 @@ class Stats(C.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def rhs_groups(nrows, max_rhs=MAX_RHS):
+    """How Solver.solve_all cuts `nrows` right-hand sides into batches of at most `max_rhs`: (first, count) pairs, full batches
+    first and the remainder last (19 -> 8 + 8 + 3)."""
+    if nrows < 0 or max_rhs < 1:
+        raise ValueError("rhs_groups: nrows >= 0 and max_rhs >= 1")
+    return [(f, min(max_rhs, nrows - f)) for f in range(0, nrows, max_rhs)]
 
 
 def lib_path():
@@ -113,6 +122,12 @@ def lib():
             "lam_hip_true_residual": ([vp, C.POINTER(C.c_double)], i32),
             "lam_hip_gemv": ([vp, vp, vp], i32),
             "lam_hip_gemv_only": ([vp, i32, C.POINTER(C.c_double)], i32),
+            "lam_hip_set_rhs_many": ([vp, i32, vp], i32),
+            "lam_hip_solve_many": ([vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_double)], i32),
+            "lam_hip_get_solution_many": ([vp, i32, vp], i32),
+            "lam_hip_gemv_many": ([vp, i32, vp, vp], i32),
+            "lam_hip_gemv_many_only": ([vp, i32, i32, C.POINTER(C.c_double)], i32),
             "lam_hip_check_symmetry": ([vp, C.POINTER(C.c_double)], i32),
             "lam_hip_debug_symv_plan": ([u64, i32, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)], i32),
             "lam_hip_dot": ([vp, vp, vp, u64, C.POINTER(C.c_double)], i32),
@@ -384,6 +399,65 @@ class Solver:
     def true_residual(self):
         v = C.c_double()
         self._chk(self._L.lam_hip_true_residual(self._h, C.byref(v)))
+        return v.value
+
+    # -- several right-hand sides on one matrix (one shard, F64 / F32) ----------------------------
+    def _as_columns(self, B):
+        B = np.ascontiguousarray(B, dtype=self.vec_dtype)
+        if B.ndim == 1:
+            B = B.reshape(1, -1)
+        assert B.ndim == 2 and B.shape[1] == self.n, "right-hand sides are (nrhs, N)"
+        return B
+
+    def set_rhs_many(self, B):
+        """B: (nrhs, N), 1 <= nrhs <= MAX_RHS; row j is right-hand side j."""
+        B = self._as_columns(B)
+        self._chk(self._L.lam_hip_set_rhs_many(self._h, B.shape[0], B.ctypes.data_as(C.c_void_p)))
+        self.nrhs = B.shape[0]
+
+    def solve_many(self, max_iters, rel_error):
+        """Independent CG recurrences for the right-hand sides of set_rhs_many, one pass over the matrix per iteration.  Returns
+        the per-column `converged` array; self.num_iters_many / converged_many / rel_err_many hold the per-column results and
+        self.stats the batch's."""
+        k = getattr(self, "nrhs", 0)
+        ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        st = Stats()
+        self._chk(self._L.lam_hip_solve_many(self._h, max_iters, rel_error, C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             cv.ctypes.data_as(C.POINTER(C.c_int32)), re.ctypes.data_as(C.POINTER(C.c_double))))
+        self.stats = st.asdict()
+        self.num_iters_many, self.converged_many, self.rel_err_many = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
+        return self.converged_many
+
+    def solutions(self):
+        """(nrhs, N): row j is the solution of right-hand side j of the last solve_many."""
+        X = np.empty((self.nrhs, self.n), dtype=self.vec_dtype)
+        self._chk(self._L.lam_hip_get_solution_many(self._h, self.nrhs, X.ctypes.data_as(C.c_void_p)))
+        return X
+
+    def solve_all(self, B, max_iters, rel_error):
+        """Any number of right-hand sides (rows of B), solved in batches of at most MAX_RHS (rhs_groups).  Returns
+        (X, num_iters, converged, rel_err), one row / entry per right-hand side."""
+        B = self._as_columns(B)
+        X = np.empty_like(B)
+        ni, cv, re = np.zeros(B.shape[0], np.int32), np.zeros(B.shape[0], bool), np.zeros(B.shape[0], np.float64)
+        for first, count in rhs_groups(B.shape[0]):
+            self.set_rhs_many(B[first:first + count])
+            self.solve_many(max_iters, rel_error)
+            X[first:first + count] = self.solutions()
+            ni[first:first + count], cv[first:first + count], re[first:first + count] = (self.num_iters_many, self.converged_many,
+                                                                                          self.rel_err_many)
+        return X, ni, cv, re
+
+    def gemv_many(self, X):
+        """Y = A X with the batched product kernel; X: (nrhs, N), row j is vector j."""
+        X = self._as_columns(X)
+        Y = np.empty_like(X)
+        self._chk(self._L.lam_hip_gemv_many(self._h, X.shape[0], X.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p)))
+        return Y
+
+    def gemv_many_only(self, nrhs, reps):
+        v = C.c_double()
+        self._chk(self._L.lam_hip_gemv_many_only(self._h, nrhs, reps, C.byref(v)))
         return v.value
 
     # -- single operators -----------------------------------------------------------------------

@@ -83,9 +83,29 @@ struct ShardBase {
     int waited_k = 0;
 };
 
+// Several right-hand sides (lam_hip_solve_many, lam_multi.h): state of its own, next to the single-vector state of the shard and
+// independent of it.  Allocated at the first batched call for LAM_HIP_MAX_RHS columns (5 vectors of 8 n elements: 21 MB at
+// n = 65536 in fp64, next to a 34 GB matrix), so it only ever grows with n; released by lam_hip_destroy and by a
+// lam_hip_set_problem that changes n.  All vectors are interleaved [n][K] (lam_kernels.h, "Several right-hand sides").
+struct MultiState {
+    uint64_t n = 0;              // the problem size the buffers were allocated for (0: none)
+    void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
+    void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out
+    double *part_gemv = nullptr; // [kMaxRhs][n]: p_j.Ap_j partials per product workgroup
+    double *part_vec = nullptr;  // [kMaxRhs][kVecBlocksMax]
+    MultiScalars *sc = nullptr, *sc_host = nullptr;   // device / pinned mirror
+    int *host_flags = nullptr;   // pinned progress word of the batch (post_progress)
+    hipEvent_t ev0[kLag] = {}, ev1[kLag] = {};        // product timing ring
+    bool timed_slot[kLag] = {};
+    int nrhs = 0, K = 0;         // right-hand sides set / instantiation they are stored for
+    bool have_rhs = false, solved = false;
+    int last_K = 0;              // option "multi_rhs_k": the K the last batched call ran
+};
+
 }  // namespace
 
 struct lam_hip_ctx {
+    MultiState multi;
     int dtype = LAM_HIP_F64;
     int total_shards = 1;          // P
     int rank = 0, nranks = 1;      // rank mode (one local shard == shard `rank`)
@@ -278,6 +298,7 @@ void matrix_changed(lam_hip_ctx *c)
     c->cg_ready = false;
     c->matrix_gen++;
     c->sym_refused = false;
+    c->multi.solved = false;
 }
 
 // ConjugateGradient_CPU_MPI_OMP.hpp:176-184: n/P rows each, the remainder on the LAST rank (lam_host_plan.h)

@@ -49,6 +49,7 @@ using namespace lam;
 #include "lam_launch.h"
 #include "lam_exchange.h"
 #include "lam_iterate.h"
+#include "lam_multi.h"
 
 
 // =================================================================================================
@@ -185,6 +186,7 @@ void lam_hip_destroy(lam_hip_ctx *c)
         (void)hipSetDevice(s.dev);
         if (s.stream) (void)hipStreamSynchronize(s.stream);
     }
+    multi_release(c);
     close_direct(c);
     if (c->agree_buf) (void)hipFree(c->agree_buf);
     for (auto &s : c->sh) {
@@ -212,6 +214,9 @@ int lam_hip_set_problem(lam_hip_ctx *c, uint64_t n)
     if (!c) return LAM_HIP_EINVAL;
     if (n == 0) return fail(c, LAM_HIP_EINVAL, "n must be > 0");
     if (n < (uint64_t)c->total_shards) return fail(c, LAM_HIP_EINVAL, "n (%llu) smaller than the number of shards", (unsigned long long)n);
+    // the batch state of lam_hip_solve_many belongs to one n: a new n releases it, the same n keeps the buffers (not the contents)
+    if (n != c->multi.n) multi_release(c);
+    c->multi.have_rhs = c->multi.solved = false;
     c->n = n;
     c->iter_est_s = 0.0;           // the observed iteration time belongs to the previous problem
     c->lda = lam_hip_ctx::pitch_for(n, c->esz_a());
@@ -1184,6 +1189,7 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "exchange_effective")) *value = c->cg_direct ? 2 : ((c->exchange1_ok() && !c->exchange2_wanted()) ? 1 : 0);
     else if (!strcmp(name, "panel_lo")) *value = c->opt_panel_lo;
     else if (!strcmp(name, "panel_hi")) *value = c->opt_panel_hi;
+    else if (!strcmp(name, "multi_rhs_k")) *value = c->multi.last_K;
     else return LAM_HIP_EINVAL;
     return 0;
 }

@@ -2420,4 +2420,344 @@ pitch_copy_kernel(const TS *__restrict__ src, uint64_t src_pitch, TD *__restrict
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Several right-hand sides on one matrix (lam_hip_solve_many, lam_multi.h): K independent CG recurrences advanced together,
+// ONE pass over the matrix per iteration.  Three launches per iteration: multi_gemv_kernel, multi_xr_kernel, multi_p_kernel.
+//
+// Layout: every batched vector (B, X, R, P, AP) is INTERLEAVED, element i of column j at [i * K + j]: the K values of p that one
+// matrix column meets are K * sizeof(TV) contiguous bytes -- 16-byte LDS reads in the product, coalesced K-wide records in the
+// vector step.  K is the instantiation (1, 2, 4, 8); nrhs <= K columns are live, the rest are zero padding columns that are born
+// stopped (MultiScalars::col[j].stop = 1 for j >= nrhs) and never touched.
+// Columns never mix: every quantity of column j is computed from column j alone, in an order that does not depend on j or on
+// what the other columns hold.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMaxRhs = 8;
+constexpr int kMultiPadRows = 16;     // zero rows kept behind row n of a batched vector (>= the 8 elements of a bf16-sized vector)
+struct MultiScalars {
+    CgScalars col[kMaxRhs];   // one recurrence per column, with CgScalars' meaning; a stopped column's entry is frozen
+    int all_stop;             // every live column has met its stop test: the batch's later launches return at once
+    int pad;
+};
+
+// p tile of the batched product: K * TILE elements of TV in LDS, 32 KiB whatever K (the single-vector fp64 kernel's figure), and at
+// least one workgroup super-step (WAVES * 64 lanes * one 16-byte vector)
+template <typename TA, typename TV, int K, int WAVES>
+constexpr int multi_tile()
+{
+    constexpr int super = WAVES * 64 * MatVec<TA>::N;
+    constexpr int fit = (int)(32768 / (K * sizeof(TV)));
+    return fit >= 4096 ? 4096 : (fit / super >= 1 ? fit / super * super : super);
+}
+
+template <typename TA, typename TV>
+struct MultiGemvArgs {
+    const TA *A;
+    const TV *p;               // [ncols + padding][K], zeros behind row n
+    TV *y;                     // [n][K]
+    double *partial;           // [K][nblocks]: column j's p_j.(A p_j) partial of workgroup b at [j * nblocks + b]; may be null
+    const MultiScalars *sc;    // may be null; sc->all_stop: nothing to do
+    uint64_t nrows, ncols, lda;
+};
+
+// Y = A P for K vectors at once: the streaming body of gemv_coop_kernel (WAVES waves share R rows, 16-byte non-temporal loads of
+// the matrix, rotated tile start, zero-filled ragged tile + kZeroVec16 for the lanes past its end, fixed-order reductions) with K
+// accumulators per row: each 16-byte piece of a row is multiplied with the K values of p of each of its columns while it is in
+// registers.
+template <typename TA, typename TV, int K, int R, int WAVES, bool NT>
+__global__ void __launch_bounds__(WAVES * 64)
+multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
+{
+    using MV = MatVec<TA>;
+    using avec_t = typename MV::vec_t;
+    constexpr int VEC = MV::N;
+    constexpr int TILE = multi_tile<TA, TV, K, WAVES>();
+    constexpr int SUPER = 64 * VEC * WAVES;             // columns one workgroup super-step covers
+    static_assert(TILE % SUPER == 0, "tile must be a whole number of workgroup super-steps");
+    constexpr int WSTEPS = TILE / SUPER;
+    constexpr int UNROLL = WSTEPS < 4 ? WSTEPS : 4;
+    constexpr int NTHREADS = WAVES * 64;
+    constexpr int PV = 16 / sizeof(TV);
+    typedef TV pvec_t __attribute__((ext_vector_type(PV)));
+    constexpr int NPV = VEC * K / PV;                   // 16-byte LDS reads per lane and step
+    static_assert((VEC * K) % PV == 0, "a lane's p values are whole 16-byte vectors");
+
+    static_assert(TILE * K >= R * K * WAVES + 2 * R * K, "the reduction scratch fits the p tile it re-uses");
+    __shared__ __attribute__((aligned(16))) TV s_p[TILE * K];
+    // the wave partials and the rows' dot products re-use the tile once the stream is done (the tile alone is 32 KiB: five
+    // workgroups per CU by LDS)
+    TV (*s_part)[WAVES] = reinterpret_cast<TV (*)[WAVES]>(s_p);
+    double *s_dot = reinterpret_cast<double *>(s_p + R * K * WAVES);
+
+    if (a.sc != nullptr && a.sc->all_stop) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const uint64_t row_first = (uint64_t)blockIdx.x * R;
+    const uint32_t woff = (uint32_t)wave * (64 * VEC) + (uint32_t)lane * VEC;
+
+    const TA *rowp[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        uint64_t row = row_first + r;
+        if (row >= a.nrows) row = a.nrows - 1;
+        rowp[r] = a.A + row * a.lda + woff;
+    }
+    TV acc[R][K];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int j = 0; j < K; j++) acc[r][j] = (TV)0;
+
+    const uint32_t ntiles = (uint32_t)((a.ncols + TILE - 1) / TILE);
+    uint32_t tt = blockIdx.x % ntiles;
+    for (uint32_t t = 0; t < ntiles; t++) {
+        const uint64_t c0 = (uint64_t)tt * TILE;
+        const uint32_t cols = (uint32_t)((a.ncols - c0 < (uint64_t)TILE) ? (a.ncols - c0) : (uint64_t)TILE);
+        __syncthreads();
+        {
+            // cols is a multiple of VEC, so cols * K elements are whole 16-byte vectors; the tile starts 16-byte aligned
+            const pvec_t *src = reinterpret_cast<const pvec_t *>(a.p + c0 * K);
+            pvec_t *dst = reinterpret_cast<pvec_t *>(s_p);
+            const uint32_t nv = cols * K / PV;
+            for (uint32_t i = tid; i < nv; i += NTHREADS) dst[i] = src[i];
+            // ragged tile: zeros up to the next whole super-step (what the lanes past the end multiply with)
+            const uint32_t padded = (cols + SUPER - 1) / SUPER * SUPER;
+            pvec_t z;
+#pragma unroll
+            for (int q = 0; q < PV; q++) z[q] = (TV)0;
+            for (uint32_t i = nv + tid; i < padded * K / PV; i += NTHREADS) dst[i] = z;
+        }
+        __syncthreads();
+        const int nsteps = cols == (uint32_t)TILE ? WSTEPS : (int)((cols + SUPER - 1) / SUPER);
+        const bool full = cols == (uint32_t)TILE;
+#pragma unroll UNROLL
+        for (int s = 0; s < nsteps; s++) {
+            const uint32_t col = (uint32_t)s * SUPER + woff;
+            avec_t av[R];
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                // lanes past the end of a ragged tile load 16 zero bytes instead of matrix elements and meet the zeros the
+                // staging put behind `cols`: they add exactly +0, whatever the row holds there
+                const avec_t *src = (full || col < cols) ? reinterpret_cast<const avec_t *>(rowp[r] + c0 + (uint64_t)s * SUPER)
+                                                         : reinterpret_cast<const avec_t *>(kZeroVec16);
+                av[r] = NT ? __builtin_nontemporal_load(src) : *src;
+            }
+            pvec_t pq[NPV];
+            const pvec_t *lp = reinterpret_cast<const pvec_t *>(s_p + (size_t)col * K);
+#pragma unroll
+            for (int q = 0; q < NPV; q++) pq[q] = lp[q];
+#pragma unroll
+            for (int i = 0; i < VEC; i++)
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    const TV pij = pq[(i * K + j) / PV][(i * K + j) % PV];
+#pragma unroll
+                    for (int r = 0; r < R; r++) acc[r][j] = fma_tv((TV)MV::get(av[r], i), pij, acc[r][j]);
+                }
+        }
+        tt = (tt + 1 == ntiles) ? 0 : tt + 1;
+    }
+
+    __syncthreads();                                    // the last tile has been consumed: s_p becomes the reduction scratch
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            TV s = wave_sum(acc[r][j]);
+            if (lane == 0) s_part[r * K + j][wave] = s;
+        }
+    __syncthreads();
+    if (tid < R * K) {
+        const int r = tid / K, j = tid % K;
+        const uint64_t row = row_first + r;
+        double d = 0.0;
+        if (row < a.nrows) {
+            TV s = s_part[tid][0];
+#pragma unroll
+            for (int w = 1; w < WAVES; w++) s += s_part[tid][w];
+            a.y[row * K + j] = s;
+            d = (double)s * (double)a.p[row * K + j];
+        }
+        s_dot[tid] = d;
+    }
+    if (a.partial != nullptr) {
+        __syncthreads();
+        if (tid < K) {
+            double t = s_dot[tid];
+#pragma unroll
+            for (int r = 1; r < R; r++) t += s_dot[r * K + tid];
+            a.partial[(size_t)tid * gridDim.x + blockIdx.x] = t;
+        }
+    }
+}
+
+// X = 0, R = P = B, per-workgroup partials of b_j.b_j at partial[j * gridDim.x + block]
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__ R, TV *__restrict__ P, uint64_t n,
+                  double *__restrict__ partial)
+{
+    __shared__ double s_red[kWaves];
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = 0.0;
+    // the kMultiPadRows rows behind the end of P are what the product's last 16-byte vector of a row meets past column n (against
+    // zeros of the row padding): zero in THIS instantiation's layout, whatever another K left there
+    if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) P[n * K + threadIdx.x] = (TV)0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const TV bi = B[i * K + j];
+            X[i * K + j] = (TV)0;
+            R[i * K + j] = bi;
+            P[i * K + j] = bi;
+            acc[j] += (double)bi * (double)bi;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// per column: bb = rr[0] = sum of its partials, iters = 0; live columns start running, padding columns are born stopped
+template <int K>
+__global__ void __launch_bounds__(kBlock)
+multi_init_scalars_kernel(const double *__restrict__ red, int nred, int nrhs, MultiScalars *sc, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    for (int j = 0; j < kMaxRhs; j++) {
+        const double t = j < K ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        if (threadIdx.x == 0) {
+            CgScalars &c = sc->col[j];
+            c.bb = t; c.rr[0] = t; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
+            c.stop = j < nrhs ? 0 : 1;
+        }
+    }
+    if (threadIdx.x == 0) {
+        sc->all_stop = 0;
+        sc->pad = 0;
+        post_progress(host_flags, 0, false);
+    }
+}
+
+// per live, running column j: alpha_j = rr_j / p_j.Ap_j ; x_j += alpha_j p_j ; r_j -= alpha_j Ap_j ; partials of r_j.r_j
+// (update_xr_kernel's statements, column by column; a stopped column is not read and not written)
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+multi_xr_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k, const TV *__restrict__ P,
+                const TV *__restrict__ AP, TV *__restrict__ X, TV *__restrict__ R, uint64_t n, double *__restrict__ partial)
+{
+    __shared__ double s_red[kWaves];
+    if (sc->all_stop) return;
+    bool run[K];
+    double alpha_d[K], pAp[K], acc[K];
+    TV alpha[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        run[j] = sc->col[j].stop == 0;
+        pAp[j] = block_sum_array(red + (size_t)j * nred, nred, s_red);
+        alpha_d[j] = sc->col[j].rr[(k + 1) & 1] / pAp[j];
+        alpha[j] = (TV)alpha_d[j];
+        acc[j] = 0.0;
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (!run[j]) continue;
+            const uint64_t e = i * K + j;
+            X[e] = alpha[j] * P[e] + X[e];
+            const TV ri = -alpha[j] * AP[e] + R[e];
+            R[e] = ri;
+            acc[j] += (double)ri * (double)ri;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) {
+            partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            if (blockIdx.x == 0 && run[j]) { sc->col[j].pAp = pAp[j]; sc->col[j].alpha = alpha_d[j]; }
+        }
+    }
+}
+
+// per running column j: rr' = r_j.r_j ; beta = rr'/rr ; if sqrt(rr'/bb_j) < tol the column stops (p_j untouched, its scalars are
+// final) else p_j = r_j + beta p_j.  The progress word reports the iteration, and "stopped" once EVERY live column has stopped.
+// Workgroup 0 is the only writer of the scalars; a workgroup that starts after it has raised a column's stop flag sees that column
+// as stopped and leaves p_j alone, which is what it would have decided itself from the same bits (update_p_kernel's argument).
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+multi_p_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k, double rel_error, const TV *__restrict__ R,
+               TV *__restrict__ P, uint64_t n, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    if (sc->all_stop) return;
+    bool upd[K];
+    TV beta[K];
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const bool run = sc->col[j].stop == 0;
+        const double rr_new = block_sum_array(red + (size_t)j * nred, nred, s_red);
+        const double rr = sc->col[j].rr[(k + 1) & 1];
+        const double bb = sc->col[j].bb;
+        const double beta_d = rr_new / rr;
+        const bool stop = sqrt(rr_new / bb) < rel_error;
+        upd[j] = run && !stop;
+        beta[j] = (TV)beta_d;
+        all = all && !upd[j];
+        if (run && blockIdx.x == 0 && threadIdx.x == 0) {
+            CgScalars &c = sc->col[j];
+            c.rr[k & 1] = rr_new;
+            c.beta = beta_d;
+            c.iters = k;
+        }
+    }
+    // a workgroup that saw a flag workgroup 0 raised in THIS launch may count a column as stopped that workgroup 0 counted as
+    // stopping: `all` is the same either way, and only workgroup 0's value is used
+    if (blockIdx.x == 0) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                if (!upd[j]) sc->col[j].stop = 1;
+            if (all) sc->all_stop = 1;
+            post_progress(host_flags, k, all);
+        }
+    }
+    if (all) return;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (!upd[j]) continue;
+            const uint64_t e = i * K + j;
+            P[e] = R[e] + beta[j] * P[e];
+        }
+    }
+}
+
+// [n][K] interleaved <-> K column vectors of n (device-side transposes of the host interface's layout)
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+multi_interleave_kernel(const TV *__restrict__ cols, int ncols, TV *__restrict__ inter, uint64_t n)
+{
+    if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) inter[n * K + threadIdx.x] = (TV)0;      // see multi_init_kernel
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++) inter[i * K + j] = j < ncols ? cols[(uint64_t)j * n + i] : (TV)0;
+}
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+multi_deinterleave_kernel(const TV *__restrict__ inter, int ncols, TV *__restrict__ cols, uint64_t n)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++)
+            if (j < ncols) cols[(uint64_t)j * n + i] = inter[i * K + j];
+}
+
 }  // namespace lam

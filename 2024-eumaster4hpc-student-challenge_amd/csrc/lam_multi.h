@@ -1,0 +1,353 @@
+// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _solve_many / _get_solution_many / _gemv_many /
+// _gemv_many_only.  nrhs independent CG recurrences (NOT block CG) advanced together, one pass over the matrix per iteration.
+// Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
+//
+// Instantiations: K = 1, 2, 4, 8 columns; nrhs runs on the smallest K >= nrhs, the K - nrhs padding columns are zero and born stopped.
+// Product shape, every K and both dtypes: 4 rows per 4-wave workgroup, p tile of 32 KiB in LDS whatever K
+// (fp64: 4096 / 2048 / 1024 / 512 columns for K = 1 / 2 / 4 / 8; fp32: 4096 / 4096 / 2048 / 1024), non-temporal matrix loads.
+// Three launches per iteration (product; x, r; p), all on shard 0's stream; the host follows the batch's own pinned progress word
+// with the lag rule of the single solve (lag_check), where "stopped" means every live column has stopped.
+#pragma once
+
+static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
+
+namespace {
+
+constexpr int kMultiRows = 4;     // rows per workgroup of multi_gemv_kernel
+constexpr int kMultiWaves = 4;    // waves per workgroup
+
+void multi_release(lam_hip_ctx *c)
+{
+    MultiState &m = c->multi;
+    if (m.n == 0) return;
+    if (c->sh.empty() || hipSetDevice(c->sh[0].dev) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (c->sh[0].stream) (void)hipStreamSynchronize(c->sh[0].stream);
+    void *dev[] = {m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.sc};
+    for (void *q : dev) if (q) (void)hipFree(q);
+    if (m.sc_host) (void)hipHostFree(m.sc_host);
+    if (m.host_flags) (void)hipHostFree(m.host_flags);
+    for (int i = 0; i < kLag; i++) {
+        if (m.ev0[i]) (void)hipEventDestroy(m.ev0[i]);
+        if (m.ev1[i]) (void)hipEventDestroy(m.ev1[i]);
+    }
+    const int last_K = m.last_K;
+    m = MultiState();
+    m.last_K = last_K;
+}
+
+// what the batched entry points serve: one process, ONE shard, fp64 / fp32 storage
+int multi_supported(lam_hip_ctx *c, const char *fn)
+{
+    if (c->rank_mode) return fail(c, LAM_HIP_EINVAL, "%s: rank mode (lam_hip_create_rank) is not supported by the multi-right-hand-side path", fn);
+    if (c->total_shards != 1)
+        return fail(c, LAM_HIP_EINVAL, "%s: %d shards: the multi-right-hand-side path supports one shard only", fn, c->total_shards);
+    if (c->dtype == LAM_HIP_BF16) return fail(c, LAM_HIP_EINVAL, "%s: LAM_HIP_BF16 storage is not supported by the multi-right-hand-side path", fn);
+    return 0;
+}
+int multi_check_nrhs(lam_hip_ctx *c, const char *fn, int nrhs)
+{
+    if (nrhs < 1 || nrhs > LAM_HIP_MAX_RHS) return fail(c, LAM_HIP_EINVAL, "%s: nrhs = %d, must be 1..%d (LAM_HIP_MAX_RHS)", fn, nrhs, LAM_HIP_MAX_RHS);
+    return 0;
+}
+int multi_k_for(int nrhs) { return nrhs <= 1 ? 1 : (nrhs <= 2 ? 2 : (nrhs <= 4 ? 4 : 8)); }
+
+int multi_ensure(lam_hip_ctx *c)
+{
+    MultiState &m = c->multi;
+    if (m.n == c->n) return 0;
+    multi_release(c);
+    ShardBase &s = c->sh[0];
+    LAMCHK(set_dev(c, s));
+    const size_t ev = c->esz_v(), elems = (size_t)(c->n + kMultiPadRows) * kMaxRhs;
+    m.n = c->n;                  // from here on multi_release gives back whatever the calls below obtained
+    void **vecs[] = {&m.B, &m.X, &m.R, &m.P, &m.AP, &m.stage};
+    for (auto v : vecs) HIPCHK(c, hipMalloc(v, elems * ev));
+    HIPCHK(c, hipMalloc((void **)&m.part_gemv, sizeof(double) * kMaxRhs * (size_t)c->n));
+    HIPCHK(c, hipMalloc((void **)&m.part_vec, sizeof(double) * kMaxRhs * kVecBlocksMax));
+    HIPCHK(c, hipMalloc((void **)&m.sc, sizeof(MultiScalars)));
+    HIPCHK(c, hipHostMalloc((void **)&m.sc_host, sizeof(MultiScalars), hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void **)&m.host_flags, 64, hipHostMallocDefault));
+    m.host_flags[0] = m.host_flags[1] = 0;
+    memset(m.sc_host, 0, sizeof(MultiScalars));
+    for (int i = 0; i < kLag; i++) {
+        HIPCHK(c, hipEventCreate(&m.ev0[i]));
+        HIPCHK(c, hipEventCreate(&m.ev1[i]));
+    }
+    // the product reads whole 16-byte vectors of a row: up to 7 columns behind the end of P are met (by zeros of the row padding),
+    // so P is zero behind row n and stays so -- the kernels write rows below n only
+    HIPCHK(c, hipMemsetAsync(m.P, 0, elems * ev, s.stream));
+    HIPCHK(c, hipMemsetAsync(m.sc, 0, sizeof(MultiScalars), s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    return 0;
+}
+
+template <typename F>
+int multi_dispatch_k(lam_hip_ctx *c, int K, F &&f)
+{
+    switch (K) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    }
+    return fail(c, LAM_HIP_EINVAL, "no batched kernels for K = %d", K);
+}
+// f(Impl<TA, TV>(), integral_constant<int, K>()) for the context's dtype (fp64 / fp32 only: multi_supported)
+template <typename F>
+int multi_dispatch(lam_hip_ctx *c, int K, F &&f)
+{
+    if (c->dtype == LAM_HIP_F64) return multi_dispatch_k(c, K, [&](auto k) -> int { return f(Impl<double, double>(), k); });
+    if (c->dtype == LAM_HIP_F32) return multi_dispatch_k(c, K, [&](auto k) -> int { return f(Impl<float, float>(), k); });
+    return fail(c, LAM_HIP_EINVAL, "the multi-right-hand-side path has no kernels for dtype %d", c->dtype);
+}
+
+int multi_gemv_grid(const lam_hip_ctx *c) { return (int)((c->n + kMultiRows - 1) / kMultiRows); }
+
+template <typename TA, typename TV, int K>
+int multi_launch_gemv(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const MultiScalars *sc)
+{
+    ShardBase &s = c->sh[0];
+    MultiGemvArgs<TA, TV> a;
+    a.A = (const TA *)s.A; a.p = P; a.y = Y; a.partial = partial; a.sc = sc;
+    a.nrows = c->n; a.ncols = c->ncols_vec(); a.lda = c->lda;
+    hipLaunchKernelGGL((multi_gemv_kernel<TA, TV, K, kMultiRows, kMultiWaves, true>), dim3(multi_gemv_grid(c)), dim3(kMultiWaves * 64), 0,
+                       s.stream, a);
+    LAUNCHED(c);
+    return 0;
+}
+
+// host layout (column j contiguous at host + j * n) -> interleaved device vector `dst` of instantiation K, padding columns zero
+int multi_upload(lam_hip_ctx *c, int nrhs, int K, const void *host, void *dst)
+{
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    HIPCHK(c, hipMemcpyAsync(m.stage, host, (size_t)nrhs * c->n * c->esz_v(), hipMemcpyHostToDevice, s.stream));
+    return multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
+        using TV = typename ImplTraits<decltype(impl)>::TV;
+        constexpr int KK = decltype(kc)::value;
+        hipLaunchKernelGGL((multi_interleave_kernel<TV, KK>), dim3(vec_grid(c->n)), dim3(kBlock), 0, s.stream, (const TV *)m.stage, nrhs,
+                           (TV *)dst, c->n);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    });
+}
+int multi_download(lam_hip_ctx *c, int nrhs, int K, const void *src, void *host)
+{
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
+        using TV = typename ImplTraits<decltype(impl)>::TV;
+        constexpr int KK = decltype(kc)::value;
+        hipLaunchKernelGGL((multi_deinterleave_kernel<TV, KK>), dim3(vec_grid(c->n)), dim3(kBlock), 0, s.stream, (const TV *)src, nrhs,
+                           (TV *)m.stage, c->n);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }));
+    HIPCHK(c, hipMemcpyAsync(host, m.stage, (size_t)nrhs * c->n * c->esz_v(), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    return 0;
+}
+
+void multi_harvest(MultiState &m, int slot, double *ms_sum, int *samples)
+{
+    if (!m.timed_slot[slot]) return;
+    m.timed_slot[slot] = false;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, m.ev0[slot], m.ev1[slot]) != hipSuccess) { (void)hipGetLastError(); return; }
+    *ms_sum += ms;
+    (*samples)++;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lam_hip_set_rhs_many(lam_hip_ctx *c, int nrhs, const void *b_host)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_set_rhs_many"));
+    LAMCHK(multi_check_nrhs(c, "lam_hip_set_rhs_many", nrhs));
+    if (!b_host) return fail(c, LAM_HIP_EINVAL, "lam_hip_set_rhs_many: b_host is NULL");
+    if (!c->have_problem) return fail(c, LAM_HIP_ESTATE, "call lam_hip_set_problem first");
+    LAMCHK(multi_ensure(c));
+    MultiState &m = c->multi;
+    m.have_rhs = m.solved = false;
+    const int K = multi_k_for(nrhs);
+    LAMCHK(multi_upload(c, nrhs, K, b_host, m.B));
+    HIPCHK(c, hipStreamSynchronize(c->sh[0].stream));
+    m.nrhs = nrhs; m.K = K;
+    m.have_rhs = true;
+    return 0;
+}
+
+int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters, int32_t *converged,
+                       double *rel_err)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_solve_many"));
+    if (max_iters < 0) return fail(c, LAM_HIP_EINVAL, "max_iters must be >= 0");
+    MultiState &m = c->multi;
+    if (!c->have_matrix || !m.have_rhs || m.n != c->n)
+        return fail(c, LAM_HIP_ESTATE, "matrix and right-hand sides (lam_hip_set_rhs_many) must be set before lam_hip_solve_many");
+    const double t0 = now_s();
+    ShardBase &s0 = c->sh[0];
+    LAMCHK(set_dev(c, s0));
+    HIPCHK(c, hipStreamSynchronize(s0.stream));
+    m.host_flags[0] = m.host_flags[1] = 0;
+    m.solved = false;
+    for (int i = 0; i < kLag; i++) m.timed_slot[i] = false;
+    c->prog_t = 0.0;
+    c->multi.last_K = m.K;
+    // the lag rule reads the batch's own progress word: the single solve's helpers on a view that carries it
+    ShardBase view;
+    view.dev = s0.dev; view.stream = s0.stream; view.host_flags = m.host_flags;
+    const int vb = vec_grid(c->n), gb = multi_gemv_grid(c);
+    double gemv_ms = 0.0;
+    int samples = 0, enq = 0;
+    LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc) -> int {
+        using I = decltype(impl);
+        using TA = typename ImplTraits<I>::TA;
+        using TV = typename ImplTraits<I>::TV;
+        constexpr int K = decltype(kc)::value;
+        // x = 0, r = p = b, bb_j = b_j.b_j
+        hipLaunchKernelGGL((multi_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X, (TV *)m.R, (TV *)m.P,
+                           c->n, m.part_vec);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((multi_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs, m.sc,
+                           (volatile int *)m.host_flags);
+        HIPCHK(c, hipGetLastError());
+        for (int i = 0; i < max_iters; i++) {
+            const int k = i + 1, slot = i % kLag;
+            if (i >= kLag) {
+                const int d = lag_check(c, view, k);
+                if (d < 0) return d;
+                if (d != 0) break;
+                multi_harvest(m, slot, &gemv_ms, &samples);
+            }
+            const double te = now_s();
+            const bool timed = timed_iteration(c, s0, k);
+            m.timed_slot[slot] = timed;
+            if (timed) RECORD(c, m.ev0[slot], s0.stream);
+            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, m.sc)));
+            if (timed) RECORD(c, m.ev1[slot], s0.stream);
+            hipLaunchKernelGGL((multi_xr_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
+                               (const TV *)m.P, (const TV *)m.AP, (TV *)m.X, (TV *)m.R, c->n, m.part_vec);
+            LAUNCHED(c);
+            hipLaunchKernelGGL((multi_p_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k, rel_error,
+                               (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags);
+            LAUNCHED(c);
+            c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
+            enq++;
+        }
+        return 0;
+    }));
+    if (enq > 0) {
+        Progress pr;
+        LAMCHK(await_progress(c, view, enq, &pr, /*precise=*/true));
+    }
+    HIPCHK(c, hipStreamSynchronize(s0.stream));
+    for (int j = 0; j < kLag; j++) multi_harvest(m, j, &gemv_ms, &samples);
+    HIPCHK(c, hipMemcpyAsync(m.sc_host, m.sc, sizeof(MultiScalars), hipMemcpyDeviceToHost, s0.stream));
+    HIPCHK(c, hipStreamSynchronize(s0.stream));
+    m.solved = true;
+    const double t1 = now_s();
+    int ran = 0, batch_iters = 0, all_conv = 1;
+    double worst = 0.0;
+    bool any_nan = false;
+    for (int j = 0; j < m.nrhs; j++) {
+        const CgScalars &sc = m.sc_host->col[j];
+        const int ni = sc.stop ? sc.iters : sc.iters + 1;
+        const double re = std::sqrt(sc.rr[sc.iters & 1] / sc.bb);
+        if (num_iters) num_iters[j] = ni;
+        if (converged) converged[j] = sc.stop != 0;
+        if (rel_err) rel_err[j] = re;
+        ran = std::max(ran, sc.iters);
+        batch_iters = std::max(batch_iters, ni);
+        all_conv = all_conv && sc.stop != 0;
+        if (re != re) any_nan = true; else worst = std::max(worst, re);
+    }
+    if (st) {
+        memset(st, 0, sizeof *st);
+        st->num_iters = batch_iters;
+        st->converged = all_conv;
+        st->rel_err = any_nan ? std::nan("") : worst;
+        st->t_total = t1 - t0;
+        st->t_iter = ran > 0 ? (t1 - t0) / ran : 0.0;
+        st->t_gemv = samples > 0 ? gemv_ms * 1e-3 / samples : 0.0;
+        st->t_comm_init = c->t_comm_init;
+        st->gemv_bytes = (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n;
+    }
+    return 0;
+}
+
+int lam_hip_get_solution_many(lam_hip_ctx *c, int nrhs, void *x_host)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_get_solution_many"));
+    LAMCHK(multi_check_nrhs(c, "lam_hip_get_solution_many", nrhs));
+    if (!x_host) return fail(c, LAM_HIP_EINVAL, "lam_hip_get_solution_many: x_host is NULL");
+    MultiState &m = c->multi;
+    if (!m.solved || m.n != c->n) return fail(c, LAM_HIP_ESTATE, "no batched solution yet (lam_hip_solve_many)");
+    if (nrhs > m.nrhs) return fail(c, LAM_HIP_EINVAL, "lam_hip_get_solution_many: %d columns asked, %d were solved", nrhs, m.nrhs);
+    LAMCHK(set_dev(c, c->sh[0]));
+    return multi_download(c, nrhs, m.K, m.X, x_host);
+}
+
+int lam_hip_gemv_many(lam_hip_ctx *c, int nrhs, const void *x_host, void *y_host)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_gemv_many"));
+    LAMCHK(multi_check_nrhs(c, "lam_hip_gemv_many", nrhs));
+    if (!x_host || !y_host) return fail(c, LAM_HIP_EINVAL, "lam_hip_gemv_many: NULL vector");
+    if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
+    LAMCHK(multi_ensure(c));
+    MultiState &m = c->multi;
+    LAMCHK(set_dev(c, c->sh[0]));
+    m.solved = false;            // P and AP of the batch are overwritten (B is not: a following lam_hip_solve_many starts from it)
+    const int K = multi_k_for(nrhs);
+    m.last_K = K;
+    LAMCHK(multi_upload(c, nrhs, K, x_host, m.P));
+    LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
+        using I = decltype(impl);
+        return multi_launch_gemv<typename ImplTraits<I>::TA, typename ImplTraits<I>::TV, decltype(kc)::value>(
+            c, (const typename ImplTraits<I>::TV *)m.P, (typename ImplTraits<I>::TV *)m.AP, nullptr, nullptr);
+    }));
+    return multi_download(c, nrhs, K, m.AP, y_host);
+}
+
+int lam_hip_gemv_many_only(lam_hip_ctx *c, int nrhs, int reps, double *sec_per_product)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_gemv_many_only"));
+    LAMCHK(multi_check_nrhs(c, "lam_hip_gemv_many_only", nrhs));
+    if (!sec_per_product || reps < 1) return fail(c, LAM_HIP_EINVAL, "lam_hip_gemv_many_only: reps must be >= 1 and the result pointer set");
+    if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
+    LAMCHK(multi_ensure(c));
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    LAMCHK(set_dev(c, s));
+    m.solved = false;
+    const int K = multi_k_for(nrhs);
+    m.last_K = K;
+    LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
+        using I = decltype(impl);
+        using TA = typename ImplTraits<I>::TA;
+        using TV = typename ImplTraits<I>::TV;
+        constexpr int KK = decltype(kc)::value;
+        // the product of a zero P: the time of a product does not depend on the vector's values, and the rows behind P's end
+        // must be zero in this K's layout
+        HIPCHK(c, hipMemsetAsync(m.P, 0, (size_t)(c->n + kMultiPadRows) * kMaxRhs * c->esz_v(), s.stream));
+        LAMCHK((multi_launch_gemv<TA, TV, KK>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, nullptr)));      // warm-up
+        HIPCHK(c, hipEventRecord(m.ev0[0], s.stream));
+        for (int i = 0; i < reps; i++) LAMCHK((multi_launch_gemv<TA, TV, KK>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, nullptr)));
+        HIPCHK(c, hipEventRecord(m.ev1[0], s.stream));
+        return 0;
+    }));
+    HIPCHK(c, hipEventSynchronize(m.ev1[0]));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, m.ev0[0], m.ev1[0]));
+    *sec_per_product = (double)ms * 1e-3 / reps;
+    return 0;
+}
+
+}  // extern "C"

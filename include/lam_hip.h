@@ -43,7 +43,10 @@ extern "C" {
  *   4  (round 5) lam_hip_stats grows by t_exchange (appended: the older fields keep their offsets, but a caller must pass
  *      the larger struct); BEHAVIOUR: the gather-Ap exchange takes any N >= shards (the reference's uneven partition), so
  *      "exchange_effective" no longer drops to 0 for N % shards != 0; lam_hip_create_rank defaults to the gather-Ap
- *      exchange too (option "exchange" = 1; was 0). */
+ *      exchange too (option "exchange" = 1; was 0).
+ *      Added under version 4 (purely additive, no struct or existing entry point changes): LAM_HIP_MAX_RHS, lam_hip_set_rhs_many,
+ *      lam_hip_solve_many, lam_hip_get_solution_many, lam_hip_gemv_many, lam_hip_gemv_many_only and the get-only option
+ *      "multi_rhs_k".  A caller that needs them checks for the symbols (dlsym) or the build id; the version number does not move. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -200,6 +203,44 @@ int lam_hip_get_solution(lam_hip_ctx *ctx, void *x_host);
  * (collective in rank mode).  Not in the reference; used for parity checks at full size. */
 int lam_hip_true_residual(lam_hip_ctx *ctx, double *rel_res);
 
+/* ---- several right-hand sides on one matrix ----------------------------------------------------
+ * nrhs INDEPENDENT CG recurrences advanced together: per iteration ONE product launch reads the matrix once for all of them
+ * (every 16-byte piece of a row meets the nrhs values of p while it is in registers), then one launch updates every x_j, r_j and
+ * one every p_j.  This is NOT block CG: column j keeps its own alpha_j, beta_j, r_j.r_j, stop decision and iteration count and
+ * follows exactly the recurrence of lam_hip_solve (x = 0, r = p = b; stop test sqrt(rr/bb) < rel_error before the p update;
+ * num_iters = max_iters + 1 at the cap).  The reference has no counterpart: its drivers are run once per right-hand-side file.
+ *   - a column that has met its stop test is FROZEN: its x, r, scalars and iteration count no longer change while the others run on;
+ *   - columns never mix: a NaN or an Inf in one column stays there.  A column with b_j = 0 gives 0/0 in the reference's loop; it
+ *     never meets the stop test, so the batch then runs to max_iters, exactly as a single solve of that column would;
+ *   - supported: single-process contexts with ONE shard, LAM_HIP_F64 and LAM_HIP_F32.  Several shards, rank mode,
+ *     LAM_HIP_BF16 and nrhs outside 1..LAM_HIP_MAX_RHS are refused with LAM_HIP_EINVAL and a message that names what is
+ *     unsupported; calls before the matrix / the right-hand sides are set give LAM_HIP_ESTATE;
+ *   - option "symmetric" (and LAM_HIP_SYMMETRIC) does NOT apply: these entry points always run the general product;
+ *   - kernels exist for K = 1, 2, 4 and 8 columns; nrhs runs on the smallest K >= nrhs with zero padding columns that are never
+ *     updated (get-only option "multi_rhs_k": the K the last batched call ran, 0 before the first);
+ *   - the batch state (vectors, scalars, progress word) is the context's own, allocated at the first batched call and independent of
+ *     b / x of the single-vector calls: lam_hip_solve and lam_hip_solve_many may be interleaved on one context and neither
+ *     disturbs the other's results.  lam_hip_set_problem invalidates the right-hand sides, as it does for lam_hip_set_rhs. */
+#define LAM_HIP_MAX_RHS 8
+/* B: nrhs vectors of N elements of the vector dtype, vector j contiguous at b_host + j*N (the layout of nrhs reference rhs files
+ * read one after the other, ConjugateGradient_CPU_MPI_OMP.hpp:258-305). */
+int lam_hip_set_rhs_many(lam_hip_ctx *ctx, int nrhs, const void *b_host);
+/* All columns from x = 0.  Returns 0 whether or not every column converged.  stats describes the batch as a whole: num_iters =
+ * the largest column's (the iterations the batch ran), converged = every column did, rel_err = the largest column's, NaN if any
+ * column's is NaN, t_gemv / t_iter / t_total / gemv_bytes as for lam_hip_solve with the batched product (gemv_bytes =
+ * esz (N^2 + 2 K N)).  num_iters / converged / rel_err: nrhs entries each, per column, with lam_hip_solve's meaning; any may be
+ * NULL. */
+int lam_hip_solve_many(lam_hip_ctx *ctx, int max_iters, double rel_error, lam_hip_stats *stats,
+                       int32_t *num_iters, int32_t *converged, double *rel_err);
+/* The first nrhs solutions of the last lam_hip_solve_many, same layout as B (vector j at x_host + j*N). */
+int lam_hip_get_solution_many(lam_hip_ctx *ctx, int nrhs, void *x_host);
+/* Y = A X with the batched product kernel, X and Y laid out as B (parity tests, roofline probe).  Leaves the right-hand sides
+ * and the single-vector state alone; a batched solution is no longer readable afterwards. */
+int lam_hip_gemv_many(lam_hip_ctx *ctx, int nrhs, const void *x_host, void *y_host);
+/* `reps` back-to-back launches of the batched product kernel for nrhs columns, timed with HIP events; *sec_per_product =
+ * average seconds per launch.  The counterpart of lam_hip_gemv_only. */
+int lam_hip_gemv_many_only(lam_hip_ctx *ctx, int nrhs, int reps, double *sec_per_product);
+
 /* ---- single operators (reference private members / CUDA kernels, for parity tests, roofline
  *      probes and callers that want the BLAS pieces) ------------------------------------------ */
 
@@ -297,7 +338,8 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *   get only: "row_pitch" (elements between rows on the device), "collectives_enqueued", "rccl_ranks" (ncclCommCount of
  *                   the context's communicator, 0 without one), "ranks_on_device", "gemv_ns_min_shard" / "gemv_ns_max_shard" (fastest /
  *                   slowest local shard's average GEMV of the last cg_iterate call: their difference is the skew), "host_cpu_ns", "host_enqueue_ns",
- *                   "hip_calls_launch" / "_record" / "_wait" / "_setdevice", "tuning_variants" (1 in the tuning build). */
+ *                   "hip_calls_launch" / "_record" / "_wait" / "_setdevice", "tuning_variants" (1 in the tuning build),
+ *                   "multi_rhs_k" (columns of the batched kernels the last lam_hip_*_many call ran: 1, 2, 4 or 8; 0 before). */
 int lam_hip_set_option(lam_hip_ctx *ctx, const char *name, int64_t value);
 int lam_hip_get_option(const lam_hip_ctx *ctx, const char *name, int64_t *value);
 
