@@ -291,6 +291,22 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
         return st.converged != 0;
     }
+    // solve_many with a preconditioner (lam_hip_solve_many_pc): precond = LAM_HIP_PC_NONE is solve_many itself, LAM_HIP_PC_JACOBI
+    // divides by the matrix's diagonal (it pays where the diagonal varies; a constant diagonal saves nothing).  No reference
+    // counterpart: the reference is un-preconditioned.  A sibling member and not an argument of solve_many, for the
+    // same reason solve_many is not virtual: only programs that call it need an ABI that has lam_hip_solve_many_pc.
+    bool solve_many_pc(int precond, int nrhs, const FloatingType *B, FloatingType *X, int max_iters, FloatingType rel_error,
+                       int32_t *num_iters = nullptr, int32_t *converged = nullptr, double *rel_err = nullptr)
+    {
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        lam_hip_stats st;
+        if (lam_hip_solve_many_pc(_ctx, precond, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0)
+            return report("solve_many_pc");
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        return st.converged != 0;
+    }
 
     // rows held by this process (all of them in the single-process classes), like the reference getters
     size_t get_num_rows() const

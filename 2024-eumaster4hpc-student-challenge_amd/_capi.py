@@ -17,6 +17,7 @@ TUNING_LIB = os.path.join(_HERE, "liblam_hip_tuning.so")
 F64, F32, BF16 = 0, 1, 2
 ABI_VERSION = 4     # include/lam_hip.h LAM_HIP_ABI_VERSION
 MAX_RHS = 8         # include/lam_hip.h LAM_HIP_MAX_RHS
+PC_NONE, PC_JACOBI = 0, 1   # include/lam_hip.h LAM_HIP_PC_*: preconditioner of Solver.solve_many / solve_all
 _VEC_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
 _HOST_MAT_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
 
@@ -125,6 +126,9 @@ def lib():
             "lam_hip_set_rhs_many": ([vp, i32, vp], i32),
             "lam_hip_solve_many": ([vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_double)], i32),
+            "lam_hip_solve_many_pc": ([vp, i32, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double)], i32),
+            "lam_hip_get_diagonal": ([vp, vp], i32),
             "lam_hip_get_solution_many": ([vp, i32, vp], i32),
             "lam_hip_gemv_many": ([vp, i32, vp, vp], i32),
             "lam_hip_gemv_many_only": ([vp, i32, i32, C.POINTER(C.c_double)], i32),
@@ -415,15 +419,19 @@ class Solver:
         self._chk(self._L.lam_hip_set_rhs_many(self._h, B.shape[0], B.ctypes.data_as(C.c_void_p)))
         self.nrhs = B.shape[0]
 
-    def solve_many(self, max_iters, rel_error):
+    def solve_many(self, max_iters, rel_error, precond=PC_NONE):
         """Independent CG recurrences for the right-hand sides of set_rhs_many, one pass over the matrix per iteration.  Returns
         the per-column `converged` array; self.num_iters_many / converged_many / rel_err_many hold the per-column results and
-        self.stats the batch's."""
+        self.stats the batch's.  precond: PC_NONE (lam_hip_solve_many) or PC_JACOBI (lam_hip_solve_many_pc, M = diag(A))."""
         k = getattr(self, "nrhs", 0)
         ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
         st = Stats()
-        self._chk(self._L.lam_hip_solve_many(self._h, max_iters, rel_error, C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)),
-                                             cv.ctypes.data_as(C.POINTER(C.c_int32)), re.ctypes.data_as(C.POINTER(C.c_double))))
+        out = (C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)), cv.ctypes.data_as(C.POINTER(C.c_int32)),
+               re.ctypes.data_as(C.POINTER(C.c_double)))
+        if precond == PC_NONE:
+            self._chk(self._L.lam_hip_solve_many(self._h, max_iters, rel_error, *out))
+        else:
+            self._chk(self._L.lam_hip_solve_many_pc(self._h, precond, max_iters, rel_error, *out))
         self.stats = st.asdict()
         self.num_iters_many, self.converged_many, self.rel_err_many = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
         return self.converged_many
@@ -434,7 +442,13 @@ class Solver:
         self._chk(self._L.lam_hip_get_solution_many(self._h, self.nrhs, X.ctypes.data_as(C.c_void_p)))
         return X
 
-    def solve_all(self, B, max_iters, rel_error):
+    def diagonal(self):
+        """The stored diagonal of the matrix (N elements of the vector dtype), extracted on the device."""
+        d = np.empty(self.n, dtype=self.vec_dtype)
+        self._chk(self._L.lam_hip_get_diagonal(self._h, d.ctypes.data_as(C.c_void_p)))
+        return d
+
+    def solve_all(self, B, max_iters, rel_error, precond=PC_NONE):
         """Any number of right-hand sides (rows of B), solved in batches of at most MAX_RHS (rhs_groups).  Returns
         (X, num_iters, converged, rel_err), one row / entry per right-hand side."""
         B = self._as_columns(B)
@@ -442,7 +456,7 @@ class Solver:
         ni, cv, re = np.zeros(B.shape[0], np.int32), np.zeros(B.shape[0], bool), np.zeros(B.shape[0], np.float64)
         for first, count in rhs_groups(B.shape[0]):
             self.set_rhs_many(B[first:first + count])
-            self.solve_many(max_iters, rel_error)
+            self.solve_many(max_iters, rel_error, precond)
             X[first:first + count] = self.solutions()
             ni[first:first + count], cv[first:first + count], re[first:first + count] = (self.num_iters_many, self.converged_many,
                                                                                           self.rel_err_many)

@@ -102,10 +102,25 @@ struct MultiState {
     int last_K = 0;              // option "multi_rhs_k": the K the last batched call ran
 };
 
+// Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,
+// extracted on the device once per matrix content (diag_gen follows lam_hip_ctx::matrix_gen, as sym_checked_gen does), the r.z
+// partials and the scalars of the preconditioned recurrences.  Lives and dies with MultiState (multi_release).
+struct PcgState {
+    uint64_t n = 0;              // the problem size the buffers were allocated for (0: none)
+    void *diag = nullptr, *dinv = nullptr;   // n elements of the vector dtype each
+    double *part_rz = nullptr;   // [kMaxRhs][kVecBlocksMax]
+    PcgScalars *sc = nullptr;    // device
+    DiagInfo *info = nullptr;    // device
+    uint64_t diag_gen = ~0ull;   // matrix_gen the diagonal was extracted from
+    uint64_t bad_count = 0, bad_row = 0;     // what that extraction found (bad_count == 0: usable)
+    double bad_value = 0.0;
+};
+
 }  // namespace
 
 struct lam_hip_ctx {
     MultiState multi;
+    PcgState pcg;
     int dtype = LAM_HIP_F64;
     int total_shards = 1;          // P
     int rank = 0, nranks = 1;      // rank mode (one local shard == shard `rank`)

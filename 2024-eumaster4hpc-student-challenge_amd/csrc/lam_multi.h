@@ -1,5 +1,6 @@
-// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _solve_many / _get_solution_many / _gemv_many /
-// _gemv_many_only.  nrhs independent CG recurrences (NOT block CG) advanced together, one pass over the matrix per iteration.
+// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _solve_many / _solve_many_pc / _get_solution_many /
+// _gemv_many / _gemv_many_only, and lam_hip_get_diagonal.  nrhs independent CG recurrences (NOT block CG) advanced together, one
+// pass over the matrix per iteration.
 // Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 //
 // Instantiations: K = 1, 2, 4, 8 columns; nrhs runs on the smallest K >= nrhs, the K - nrhs padding columns are zero and born stopped.
@@ -19,9 +20,12 @@ constexpr int kMultiWaves = 4;    // waves per workgroup
 void multi_release(lam_hip_ctx *c)
 {
     MultiState &m = c->multi;
-    if (m.n == 0) return;
+    if (m.n == 0) return;        // the preconditioner's state is allocated behind the batch's only (pcg_ensure)
     if (c->sh.empty() || hipSetDevice(c->sh[0].dev) != hipSuccess) { (void)hipGetLastError(); return; }
     if (c->sh[0].stream) (void)hipStreamSynchronize(c->sh[0].stream);
+    void *pdev[] = {c->pcg.diag, c->pcg.dinv, c->pcg.part_rz, c->pcg.sc, c->pcg.info};
+    for (void *q : pdev) if (q) (void)hipFree(q);
+    c->pcg = PcgState();
     void *dev[] = {m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.sc};
     for (void *q : dev) if (q) (void)hipFree(q);
     if (m.sc_host) (void)hipHostFree(m.sc_host);
@@ -148,6 +152,63 @@ int multi_download(lam_hip_ctx *c, int nrhs, int K, const void *src, void *host)
     return 0;
 }
 
+// The Jacobi preconditioner of lam_hip_solve_many_pc.  No reference counterpart: the reference is un-preconditioned.
+int pcg_ensure(lam_hip_ctx *c)
+{
+    PcgState &g = c->pcg;
+    if (g.n == c->n) return 0;
+    ShardBase &s = c->sh[0];
+    LAMCHK(set_dev(c, s));
+    void *old[] = {g.diag, g.dinv, g.part_rz, g.sc, g.info};
+    for (void *q : old) if (q) (void)hipFree(q);
+    g = PcgState();              // g.n == 0 until everything below has succeeded: a failure is retried, never launched on
+    HIPCHK(c, hipMalloc(&g.diag, c->n * c->esz_v()));
+    HIPCHK(c, hipMalloc(&g.dinv, c->n * c->esz_v()));
+    HIPCHK(c, hipMalloc((void **)&g.part_rz, sizeof(double) * kMaxRhs * kVecBlocksMax));
+    HIPCHK(c, hipMalloc((void **)&g.sc, sizeof(PcgScalars)));
+    HIPCHK(c, hipMalloc((void **)&g.info, sizeof(DiagInfo)));
+    HIPCHK(c, hipMemsetAsync(g.sc, 0, sizeof(PcgScalars), s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    g.n = c->n;
+    return 0;
+}
+
+// diag / dinv of the matrix held now: one launch over the n diagonal elements of the pitched matrix, once per matrix content
+// (matrix_gen).  The scan for rows that cannot be inverted is part of that launch; the host reads a count, the first such row and,
+// if there is one, that row's value -- never the n values.
+int pcg_extract_diagonal(lam_hip_ctx *c)
+{
+    PcgState &g = c->pcg;
+    if (g.diag_gen == c->matrix_gen) return 0;
+    ShardBase &s = c->sh[0];
+    DiagInfo h;
+    h.first_bad = ~0ull; h.count = 0;
+    HIPCHK(c, hipMemcpyAsync(g.info, &h, sizeof h, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));      // h is pageable
+    LAMCHK(multi_dispatch(c, 1, [&](auto impl, auto) -> int {
+        using TA = typename ImplTraits<decltype(impl)>::TA;
+        using TV = typename ImplTraits<decltype(impl)>::TV;
+        hipLaunchKernelGGL((diag_extract_kernel<TA, TV>), dim3(vec_grid(c->n)), dim3(kBlock), 0, s.stream, (const TA *)s.A, c->lda,
+                           (uint64_t)0, c->n, (TV *)g.diag, (TV *)g.dinv, g.info);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }));
+    HIPCHK(c, hipMemcpyAsync(&h, g.info, sizeof h, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    g.bad_count = h.count;
+    g.bad_row = h.first_bad;
+    g.bad_value = 0.0;
+    if (h.count != 0 && h.first_bad < c->n) {
+        double v64 = 0.0;
+        float v32 = 0.f;
+        void *dst = c->dtype == LAM_HIP_F64 ? (void *)&v64 : (void *)&v32;
+        HIPCHK(c, hipMemcpy(dst, (const char *)g.diag + h.first_bad * c->esz_v(), c->esz_v(), hipMemcpyDeviceToHost));
+        g.bad_value = c->dtype == LAM_HIP_F64 ? v64 : (double)v32;
+    }
+    g.diag_gen = c->matrix_gen;
+    return 0;
+}
+
 void multi_harvest(MultiState &m, int slot, double *ms_sum, int *samples)
 {
     if (!m.timed_slot[slot]) return;
@@ -180,21 +241,40 @@ int lam_hip_set_rhs_many(lam_hip_ctx *c, int nrhs, const void *b_host)
     return 0;
 }
 
-int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters, int32_t *converged,
-                       double *rel_err)
+}  // extern "C"
+
+namespace {
+
+// lam_hip_solve_many (precond = LAM_HIP_PC_NONE) and lam_hip_solve_many_pc: one body.  The plain batch launches exactly what it
+// always did; the Jacobi-preconditioned one swaps the two vector kernels and the initialisation for their pcg_* counterparts and
+// keeps its scalars in PcgState (the plain batch's device scalars are not touched), the product launch, the progress word, the
+// lag rule and the per-column results are shared.
+int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters,
+                int32_t *converged, double *rel_err)
 {
-    if (!c) return LAM_HIP_EINVAL;
-    LAMCHK(multi_supported(c, "lam_hip_solve_many"));
+    LAMCHK(multi_supported(c, fn));
+    if (precond != LAM_HIP_PC_NONE && precond != LAM_HIP_PC_JACOBI)
+        return fail(c, LAM_HIP_EINVAL, "%s: unknown preconditioner %d (LAM_HIP_PC_NONE, LAM_HIP_PC_JACOBI)", fn, precond);
+    const bool pc = precond == LAM_HIP_PC_JACOBI;
     if (max_iters < 0) return fail(c, LAM_HIP_EINVAL, "max_iters must be >= 0");
     MultiState &m = c->multi;
     if (!c->have_matrix || !m.have_rhs || m.n != c->n)
-        return fail(c, LAM_HIP_ESTATE, "matrix and right-hand sides (lam_hip_set_rhs_many) must be set before lam_hip_solve_many");
+        return fail(c, LAM_HIP_ESTATE, "matrix and right-hand sides (lam_hip_set_rhs_many) must be set before %s", fn);
     const double t0 = now_s();
     ShardBase &s0 = c->sh[0];
     LAMCHK(set_dev(c, s0));
     HIPCHK(c, hipStreamSynchronize(s0.stream));
+    PcgState &g = c->pcg;
+    m.solved = false;            // whatever follows, a refusal of the diagonal included, leaves no batched solution behind
+    if (pc) {
+        LAMCHK(pcg_ensure(c));
+        LAMCHK(pcg_extract_diagonal(c));
+        if (g.bad_count != 0)
+            return fail(c, LAM_HIP_EINVAL, "%s: the Jacobi preconditioner needs A[i][i] and 1/A[i][i] finite and > 0: row %llu holds %g "
+                        "(%llu such rows)", fn, (unsigned long long)g.bad_row, g.bad_value, (unsigned long long)g.bad_count);
+    }
+    MultiScalars *const sc_dev = pc ? &g.sc->m : m.sc;
     m.host_flags[0] = m.host_flags[1] = 0;
-    m.solved = false;
     for (int i = 0; i < kLag; i++) m.timed_slot[i] = false;
     c->prog_t = 0.0;
     c->multi.last_K = m.K;
@@ -209,13 +289,23 @@ int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_
         using TA = typename ImplTraits<I>::TA;
         using TV = typename ImplTraits<I>::TV;
         constexpr int K = decltype(kc)::value;
-        // x = 0, r = p = b, bb_j = b_j.b_j
-        hipLaunchKernelGGL((multi_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X, (TV *)m.R, (TV *)m.P,
-                           c->n, m.part_vec);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL((multi_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs, m.sc,
-                           (volatile int *)m.host_flags);
-        HIPCHK(c, hipGetLastError());
+        if (!pc) {
+            // x = 0, r = p = b, bb_j = b_j.b_j
+            hipLaunchKernelGGL((multi_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X, (TV *)m.R,
+                               (TV *)m.P, c->n, m.part_vec);
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL((multi_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs,
+                               m.sc, (volatile int *)m.host_flags);
+            HIPCHK(c, hipGetLastError());
+        } else {
+            // x = 0, r = b, p = dinv o b, bb_j = b_j.b_j, rz_j = b_j.(dinv o b_j)
+            hipLaunchKernelGGL((pcg_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (const TV *)g.dinv, (TV *)m.X,
+                               (TV *)m.R, (TV *)m.P, c->n, m.part_vec, g.part_rz);
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL((pcg_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec,
+                               (const double *)g.part_rz, vb, m.nrhs, g.sc, (volatile int *)m.host_flags);
+            HIPCHK(c, hipGetLastError());
+        }
         for (int i = 0; i < max_iters; i++) {
             const int k = i + 1, slot = i % kLag;
             if (i >= kLag) {
@@ -228,14 +318,24 @@ int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_
             const bool timed = timed_iteration(c, s0, k);
             m.timed_slot[slot] = timed;
             if (timed) RECORD(c, m.ev0[slot], s0.stream);
-            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, m.sc)));
+            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, sc_dev)));
             if (timed) RECORD(c, m.ev1[slot], s0.stream);
-            hipLaunchKernelGGL((multi_xr_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
-                               (const TV *)m.P, (const TV *)m.AP, (TV *)m.X, (TV *)m.R, c->n, m.part_vec);
-            LAUNCHED(c);
-            hipLaunchKernelGGL((multi_p_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k, rel_error,
-                               (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags);
-            LAUNCHED(c);
+            if (!pc) {
+                hipLaunchKernelGGL((multi_xr_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
+                                   (const TV *)m.P, (const TV *)m.AP, (TV *)m.X, (TV *)m.R, c->n, m.part_vec);
+                LAUNCHED(c);
+                hipLaunchKernelGGL((multi_p_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k,
+                                   rel_error, (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags);
+                LAUNCHED(c);
+            } else {
+                hipLaunchKernelGGL((pcg_xr_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, g.sc, k,
+                                   (const TV *)m.P, (const TV *)m.AP, (const TV *)g.dinv, (TV *)m.X, (TV *)m.R, c->n, m.part_vec, g.part_rz);
+                LAUNCHED(c);
+                hipLaunchKernelGGL((pcg_p_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec,
+                                   (const double *)g.part_rz, vb, g.sc, k, rel_error, (const TV *)m.R, (const TV *)g.dinv, (TV *)m.P, c->n,
+                                   (volatile int *)m.host_flags);
+                LAUNCHED(c);
+            }
             c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
             enq++;
         }
@@ -247,7 +347,7 @@ int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_
     }
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     for (int j = 0; j < kLag; j++) multi_harvest(m, j, &gemv_ms, &samples);
-    HIPCHK(c, hipMemcpyAsync(m.sc_host, m.sc, sizeof(MultiScalars), hipMemcpyDeviceToHost, s0.stream));
+    HIPCHK(c, hipMemcpyAsync(m.sc_host, sc_dev, sizeof(MultiScalars), hipMemcpyDeviceToHost, s0.stream));
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     m.solved = true;
     const double t1 = now_s();
@@ -275,9 +375,52 @@ int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_
         st->t_iter = ran > 0 ? (t1 - t0) / ran : 0.0;
         st->t_gemv = samples > 0 ? gemv_ms * 1e-3 / samples : 0.0;
         st->t_comm_init = c->t_comm_init;
+        // the product launch alone, with or without the preconditioner: the diagonal is read by the two vector launches
         st->gemv_bytes = (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n;
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters, int32_t *converged,
+                       double *rel_err)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    return multi_solve(c, "lam_hip_solve_many", LAM_HIP_PC_NONE, max_iters, rel_error, st, num_iters, converged, rel_err);
+}
+
+int lam_hip_solve_many_pc(lam_hip_ctx *c, int precond, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters,
+                          int32_t *converged, double *rel_err)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    return multi_solve(c, "lam_hip_solve_many_pc", precond, max_iters, rel_error, st, num_iters, converged, rel_err);
+}
+
+// Single-process contexts, any number of shards, every storage type: each shard's device extracts its own rows' diagonal elements.
+int lam_hip_get_diagonal(lam_hip_ctx *c, void *d_host)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    if (c->rank_mode) return fail(c, LAM_HIP_EINVAL, "lam_hip_get_diagonal: rank mode (lam_hip_create_rank) is not supported");
+    if (!d_host) return fail(c, LAM_HIP_EINVAL, "lam_hip_get_diagonal: d_host is NULL");
+    if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
+    return dispatch(c, [&](auto impl) -> int {
+        using TA = typename ImplTraits<decltype(impl)>::TA;
+        using TV = typename ImplTraits<decltype(impl)>::TV;
+        for (auto &s : c->sh) {      // no shard is empty: lam_hip_set_problem refuses n < shards
+            LAMCHK(set_dev(c, s));
+            DevBuf d;
+            HIPCHK(c, hipMalloc(&d.p, s.nrows * sizeof(TV)));
+            hipLaunchKernelGGL((diag_extract_kernel<TA, TV>), dim3(vec_grid(s.nrows)), dim3(kBlock), 0, s.stream, (const TA *)s.A, c->lda,
+                               s.row0, s.nrows, d.as<TV>(), (TV *)nullptr, (DiagInfo *)nullptr);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync((TV *)d_host + s.row0, d.p, s.nrows * sizeof(TV), hipMemcpyDeviceToHost, s.stream));
+            HIPCHK(c, hipStreamSynchronize(s.stream));
+        }
+        return 0;
+    });
 }
 
 int lam_hip_get_solution_many(lam_hip_ctx *c, int nrhs, void *x_host)

@@ -46,7 +46,9 @@ extern "C" {
  *      exchange too (option "exchange" = 1; was 0).
  *      Added under version 4 (purely additive, no struct or existing entry point changes): LAM_HIP_MAX_RHS, lam_hip_set_rhs_many,
  *      lam_hip_solve_many, lam_hip_get_solution_many, lam_hip_gemv_many, lam_hip_gemv_many_only and the get-only option
- *      "multi_rhs_k".  A caller that needs them checks for the symbols (dlsym) or the build id; the version number does not move. */
+ *      "multi_rhs_k".  A caller that needs them checks for the symbols (dlsym) or the build id; the version number does not move.
+ *      Added under version 4 likewise (purely additive): LAM_HIP_PC_NONE, LAM_HIP_PC_JACOBI, lam_hip_solve_many_pc and
+ *      lam_hip_get_diagonal. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -232,7 +234,42 @@ int lam_hip_set_rhs_many(lam_hip_ctx *ctx, int nrhs, const void *b_host);
  * NULL. */
 int lam_hip_solve_many(lam_hip_ctx *ctx, int max_iters, double rel_error, lam_hip_stats *stats,
                        int32_t *num_iters, int32_t *converged, double *rel_err);
-/* The first nrhs solutions of the last lam_hip_solve_many, same layout as B (vector j at x_host + j*N). */
+/* lam_hip_solve_many with a preconditioner.  precond = LAM_HIP_PC_NONE is lam_hip_solve_many itself (same code, same bits).
+ * No reference counterpart: the reference is un-preconditioned.
+ * LAM_HIP_PC_JACOBI: M = diag(A).  Per column j, independently, with dinv_i = 1 / A[i][i] computed in fp64 from the stored value
+ * and rounded to the vector dtype:
+ *     x = 0, r = b, bb = b.b, p = z = dinv o b, rz = r.z
+ *     k = 1..max_iters:  Ap = A p;  alpha = rz / p.Ap;  x += alpha p;  r -= alpha Ap;  rr' = r.r;  rz' = r.(dinv o r)
+ *                        if sqrt(rr'/bb) < rel_error: stop (p untouched);  beta = rz'/rz;  p = dinv o r + beta p
+ * The stop test is lam_hip_solve's, on the same quantity (the UNpreconditioned recursive residual), so rel_error means the same
+ * with and without the preconditioner.  Three launches per iteration as before, the product launch is the same kernel; the two
+ * vector launches read one more vector of N elements each (N against N^2 matrix elements).  Measured at N = 65536 fp64 and
+ * N = 131072 fp32, K = 1, 4, 8: an iteration costs 0.9945 ... 1.0004 of a plain one, inside the plain path's run-to-run spread
+ * (profiles/pcg_probe.txt; the two vector kernels together take 7 us more at K = 8, profiles/pcg_k8_kernel_stats.txt), so at
+ * such sizes every iteration saved is a pass over the matrix saved.
+ *   - supports exactly what lam_hip_solve_many supports and refuses the same cases with the same codes; an unknown `precond`
+ *     gives LAM_HIP_EINVAL;
+ *   - the per-column arrays, the stats, lam_hip_get_solution_many, the frozen state of a stopped column, max_iters + 1 at the cap,
+ *     the confinement of NaN / Inf to their column, a b_j = 0 column running to the cap on 0/0 and option "multi_rhs_k" are those
+ *     of lam_hip_solve_many.  gemv_bytes counts the product launch alone, esz (N^2 + 2 K N) as without the preconditioner: the
+ *     diagonal is read by the vector launches, not by the product;
+ *   - the diagonal is extracted on the device once per matrix content (an upload or a generator call is seen by the next solve);
+ *     a row whose A[i][i] or whose dinv_i is not finite and > 0 (<= 0, either zero, NaN, Inf, a subnormal whose reciprocal
+ *     overflows) is refused with LAM_HIP_EINVAL and a message that names the first such row and its value: nothing is iterated
+ *     and there is no batched solution afterwards (lam_hip_get_solution_many: LAM_HIP_ESTATE);
+ *   - where it helps: matrices whose diagonal varies (lam_hip_generate_random_spd, badly scaled systems S M S).  For a CONSTANT
+ *     diagonal -- lam_hip_generate_tridiag, the heat assembler's matrix, the reference generator's Q D Q^T in expectation -- the
+ *     preconditioned recurrence is the plain one up to a scale factor and saves nothing. */
+#define LAM_HIP_PC_NONE   0
+#define LAM_HIP_PC_JACOBI 1
+int lam_hip_solve_many_pc(lam_hip_ctx *ctx, int precond, int max_iters, double rel_error, lam_hip_stats *stats,
+                          int32_t *num_iters, int32_t *converged, double *rel_err);
+/* The stored diagonal A[i][i], N elements of the vector dtype (LAM_HIP_BF16 storage: the stored bf16 values as float, exactly),
+ * extracted on the device(s) from the pitched matrix.  Single-process contexts with any number of shards, every storage type;
+ * rank mode: LAM_HIP_EINVAL; no matrix set: LAM_HIP_ESTATE.  No reference counterpart: the reference is un-preconditioned
+ * (SURVEY §1). */
+int lam_hip_get_diagonal(lam_hip_ctx *ctx, void *d_host);
+/* The first nrhs solutions of the last lam_hip_solve_many / lam_hip_solve_many_pc, same layout as B (vector j at x_host + j*N). */
 int lam_hip_get_solution_many(lam_hip_ctx *ctx, int nrhs, void *x_host);
 /* Y = A X with the batched product kernel, X and Y laid out as B (parity tests, roofline probe).  Leaves the right-hand sides
  * and the single-vector state alone; a batched solution is no longer readable afterwards. */
