@@ -10,10 +10,20 @@ Why the answers are exact:
   * p.Ap with p = b: every term |b_i (A b)_i| <= 8 * 64 n, so p.Ap <= 512 n^2 (< 2^53 up to n ~ 4e6) and b.b <= 64 n are exact
     in the fp64 reductions whatever their order;
   * bf16 has 8 significant bits: every integer of magnitude <= 256 is exact, so bf16 storage holds the matrix as it is.
-The host reference (fp64 BLAS on integer blocks) is therefore exact too."""
+The host reference (fp64 BLAS on integer blocks) is therefore exact too.
+
+With a power-of-two diagonal (generate(..., diag=d), d_i in {1, 2, 4, 8}: the first JACOBI step, first_pcg_step):
+  * dinv_i = 1 / d_i and z0 = dinv o b are exact, z0 a multiple of 1/8 of magnitude <= 8; r.z = sum b_i^2 / d_i is a multiple of 1/8
+    below 64 n;
+  * every product A[i, j] z0[j] is a multiple of 1/8 of magnitude <= 64 (the diagonal's: d_i z0_i = b_i), so every partial sum of a
+    row of A z0 is a multiple of 1/8 of magnitude <= 64 n, i.e. an integer <= 8 * 64 n in units of 1/8: fp64 holds it exactly; fp32
+    while 8 * 64 n < 2^24, i.e. n <= 32767;
+  * p.Ap with p = z0: multiples of 1/64, |z0_i (A z0)_i| <= 8 * 64 n, the sum <= 512 n^2: exact in fp64 in any order.
+An integer vector x against the patched matrix stays under the first set of bounds (|d_i x_i| <= 64)."""
 import numpy as np
 
 MAX_EXACT_N_FP32 = (1 << 24) // 64 - 1          # 262143: 64 n < 2^24
+MAX_EXACT_N_FP32_JACOBI = (1 << 24) // (8 * 64) - 1     # 32767: 8 * 64 n < 2^24 (A z0 in eighths)
 
 
 def _keys(n):
@@ -46,8 +56,19 @@ def block_rows(n, elems=1 << 24):
     return max(1, elems // max(n, 1))
 
 
-def generate(n, sinks, vecs):
-    """Stream the matrix through every `sink(row0, block)` and return A @ v for each v of `vecs` (exact: integer fp64 BLAS)."""
+def pow2_diagonal(n, seed):
+    """d_i drawn from {1, 2, 4, 8}, no two neighbouring rows alike (a repeat is moved on to the next power, cyclically)."""
+    e = np.random.default_rng(seed).integers(0, 4, n)
+    for i in range(1, n):
+        if e[i] == e[i - 1]:
+            e[i] = (e[i] + 1) % 4
+    return 2.0 ** e
+
+
+def generate(n, sinks, vecs, diag=None):
+    """Stream the matrix through every `sink(row0, block)` and return A @ v for each v of `vecs` (exact: integer fp64 BLAS).
+    diag (optional, n values): the matrix's diagonal is replaced by it -- each block is patched before it reaches the sinks and the
+    returned products are the unpatched ones corrected by (d_i - A_ii) v_i."""
     assert n <= MAX_EXACT_N_FP32
     V = np.stack(vecs, axis=1) if vecs else np.zeros((n, 0))
     out = np.empty((n, V.shape[1]))
@@ -55,9 +76,13 @@ def generate(n, sinks, vecs):
     for r0 in range(0, n, step):
         r1 = min(n, r0 + step)
         blk = int_block(r0, r1, n, keys)
+        out[r0:r1] = blk @ V
+        if diag is not None:
+            i = np.arange(r1 - r0)
+            out[r0:r1] += (diag[r0:r1] - blk[i, r0 + i])[:, None] * V[r0:r1]
+            blk[i, r0 + i] = diag[r0:r1]
         for sink in sinks:
             sink(r0, blk)
-        out[r0:r1] = blk @ V
     return [out[:, k] for k in range(V.shape[1])]
 
 
@@ -74,6 +99,34 @@ def first_cg_step(b, Ab, vec_dtype):
     x1 = alpha_tv * b.astype(vec_dtype)                 # numpy: one correctly rounded multiply in vec_dtype
     r1 = b - np.float64(alpha_tv) * Ab
     return alpha_tv, x1, bb, pAp, r1
+
+
+def first_pcg_step(b, d, Az, vec_dtype):
+    """The first Jacobi-preconditioned step from x = 0 as pcg_init_kernel / pcg_xr_kernel compute it, for integer b, a power-of-two
+    diagonal d and Az = A z0 with z0 = b / d (exact):  alpha = fl64(r.z / p.Ap) with r.z = sum b_i z0_i and p.Ap = sum z0_i (A z0)_i
+    both exact, rounded once to the vector type, x1 = fl(alpha_TV * z0).  Returns (alpha_TV, x1, bb, r1) with bb = b.b and
+    r1 = b - alpha_TV A z0 in fp64."""
+    assert np.all((d == 1) | (d == 2) | (d == 4) | (d == 8))
+    z0 = b / d
+    z8, Az8, bi = np.rint(8 * z0).astype(np.int64), np.rint(8 * Az).astype(np.int64), b.astype(np.int64)
+    assert np.array_equal(z8 / 8.0, z0) and np.array_equal(Az8 / 8.0, Az), "z0 and A z0 are multiples of 1/8"
+    bb, rz8, pAp64 = int((bi * bi).sum()), int((bi * z8).sum()), int((z8 * Az8).sum())
+    assert pAp64 != 0, "p.Ap = 0: the first step is undefined"
+    assert abs(pAp64) < 2 ** 53 and rz8 < 2 ** 53 and bb < 2 ** 53
+    alpha = np.float64(rz8 / 8.0) / np.float64(pAp64 / 64.0)      # both operands exact in fp64: one correctly rounded division
+    alpha_tv = vec_dtype(alpha)
+    x1 = alpha_tv * z0.astype(vec_dtype)
+    r1 = b - np.float64(alpha_tv) * Az
+    return alpha_tv, x1, bb, r1
+
+
+def tridiag_product(x):
+    """y = tridiag(1, 2, 1) x for one vector or the rows of a 2-D array (the device-side generator's matrix)."""
+    x = np.asarray(x, np.float64)
+    y = 2.0 * x
+    y[..., 1:] += x[..., :-1]
+    y[..., :-1] += x[..., 1:]
+    return y
 
 
 def rel_err_bound(b, Ab, alpha_tv, r1, bb, u_tv):

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from tracking_data import ITERATION_TRACKING_GATES, iteration_tracking_system
 
 pytestmark = pytest.mark.gpu
 
@@ -190,17 +191,11 @@ def test_cg_matches_oracle_iteration_by_iteration(lam, oracle):
     Tolerances come from the reference algorithm's own sensitivity to summation order on this system
     (oracle at 1 thread vs the oracle with 4/8 threads or 3 emulated ranks): <= 1.6e-14 in the residual
     and <= 2.4e-12 in x up to k=40, then chaotic (4e-3 / 4e-6 at k=60: orthogonality is lost)."""
-    n = 384
-    rng = np.random.default_rng(9)
-    q, _ = np.linalg.qr(rng.uniform(-1, 1, (n, n)))
-    A = (q * np.exp(3.0 * rng.uniform(-1, 1, n))) @ q.T
-    A = 0.5 * (A + A.T)
-    b = rng.uniform(-1, 1, n)
+    A, b = iteration_tracking_system()
     with lam.Solver(lam.F64) as s:
         s.set_matrix(A)
         s.set_rhs(b)
-        for k, tol_res, tol_x in ((1, 1e-13, 1e-13), (2, 1e-13, 1e-13), (5, 1e-13, 1e-13), (20, 1e-12, 1e-12),
-                                  (40, 1e-11, 1e-10), (60, 5e-2, 5e-5)):
+        for k, tol_res, tol_x in ITERATION_TRACKING_GATES:
             s.solve(k, 1e-30)
             x_ref, st_ref = oracle.cg_solve(A, b, k, 1e-30)
             assert s.stats["num_iters"] == k + 1 == st_ref["num_iters"]
