@@ -93,7 +93,8 @@ struct MultiState {
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out
     double *part_gemv = nullptr; // [kMaxRhs][n]: p_j.Ap_j partials per product workgroup
     double *part_vec = nullptr;  // [kMaxRhs][kVecBlocksMax]
-    MultiScalars *sc = nullptr, *sc_host = nullptr;   // device / pinned mirror
+    BatchScalars *sc = nullptr;  // device; every solve re-initialises it in its init launch
+    MultiScalars *sc_host = nullptr;                  // pinned mirror of its MultiScalars prefix
     int *host_flags = nullptr;   // pinned progress word of the batch (post_progress)
     hipEvent_t ev0[kLag] = {}, ev1[kLag] = {};        // product timing ring
     bool timed_slot[kLag] = {};
@@ -103,14 +104,12 @@ struct MultiState {
 };
 
 // Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,
-// extracted on the device once per matrix content (diag_gen follows lam_hip_ctx::matrix_gen, as sym_checked_gen does), the r.z
-// partials and the scalars of the preconditioned recurrences.  Lives and dies with MultiState (multi_release).
+// extracted on the device once per matrix content (diag_gen follows lam_hip_ctx::matrix_gen, as sym_checked_gen does), and the r.z
+// partials.  Allocated by the first preconditioned solve (pcg_ensure) for the batch's n; lives and dies with MultiState (multi_release).
 struct PcgState {
-    uint64_t n = 0;              // the problem size the buffers were allocated for (0: none)
     void *diag = nullptr, *dinv = nullptr;   // n elements of the vector dtype each
     double *part_rz = nullptr;   // [kMaxRhs][kVecBlocksMax]
-    PcgScalars *sc = nullptr;    // device
-    DiagInfo *info = nullptr;    // device
+    DiagInfo *info = nullptr;    // device; the last of the four to be allocated: set means all are
     uint64_t diag_gen = ~0ull;   // matrix_gen the diagonal was extracted from
     uint64_t bad_count = 0, bad_row = 0;     // what that extraction found (bad_count == 0: usable)
     double bad_value = 0.0;

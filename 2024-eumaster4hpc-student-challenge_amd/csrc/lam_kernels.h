@@ -2432,13 +2432,28 @@ pitch_copy_kernel(const TS *__restrict__ src, uint64_t src_pitch, TD *__restrict
 // stopped (MultiScalars::col[j].stop = 1 for j >= nrhs) and never touched.
 // Columns never mix: every quantity of column j is computed from column j alone, in an order that does not depend on j or on
 // what the other columns hold.
+//
+// The vector kernels carry a compile-time PC: false is the plain recurrence, true the Jacobi-preconditioned one of
+// lam_hip_solve_many_pc, M = diag(A) (no reference counterpart: the reference is un-preconditioned).  The delta:
+//   x = 0, r = b, p = z = dinv o b, rz = r.z ;  alpha = rz / p.Ap ; x += alpha p ; r -= alpha Ap ; rr' = r.r ; rz' = r.(dinv o r) ;
+//   stop test on sqrt(rr'/bb) as in the plain recurrence ; beta = rz'/rz ; p = dinv o r + beta p
+// z is never stored: dinv (one vector of n elements shared by the K columns, read once per row) is applied where z is needed, and
+// r.z gets a second set of partials, reduced right behind r.r's by the same building blocks.  Everything else is the one set of
+// statements, so on a matrix whose diagonal is a constant power of two every quantity is the plain recurrence's times an exact power
+// of two and x, the iteration counts and rel_err agree bit for bit.  With PC = false, dinv and the r.z partials are null and never
+// dereferenced.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxRhs = 8;
 constexpr int kMultiPadRows = 16;     // zero rows kept behind row n of a batched vector (>= the 8 elements of a bf16-sized vector)
 struct MultiScalars {
-    CgScalars col[kMaxRhs];   // one recurrence per column, with CgScalars' meaning; a stopped column's entry is frozen
+    CgScalars col[kMaxRhs];   // one recurrence per column, with CgScalars' meaning; a stopped column's entry is frozen (under the
+                              // preconditioner alpha and beta are the preconditioned ones)
     int all_stop;             // every live column has met its stop test: the batch's later launches return at once
     int pad;
+};
+// the batch's device block: the MultiScalars prefix is what the product kernel reads and the host copies back
+struct BatchScalars : MultiScalars {
+    double rz[kMaxRhs][2];    // PC only: r_j.z_j, ping-pong like CgScalars::rr: iteration k reads [(k+1)&1], writes [k&1]
 };
 
 // p tile of the batched product: K * TILE elements of TV in LDS, 32 KiB whatever K (the single-vector fp64 kernel's figure), and at
@@ -2594,48 +2609,71 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
     }
 }
 
-// X = 0, R = P = B, per-workgroup partials of b_j.b_j at partial[j * gridDim.x + block]
-template <typename TV, int K>
+// X = 0, R = B, P = B (PC: dinv o B); per-workgroup partials of b_j.b_j (PC: and of r_j.z_j = b_j.(dinv o b_j)), both at
+// [j * gridDim.x + block]
+template <typename TV, int K, bool PC>
 __global__ void __launch_bounds__(kBlock)
 multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__ R, TV *__restrict__ P, uint64_t n,
-                  double *__restrict__ partial)
+                  double *__restrict__ partial, const TV *__restrict__ dinv, double *__restrict__ partial_rz)
 {
     __shared__ double s_red[kWaves];
     double acc[K];
+    [[maybe_unused]] double accz[K];
 #pragma unroll
-    for (int j = 0; j < K; j++) acc[j] = 0.0;
+    for (int j = 0; j < K; j++) {
+        acc[j] = 0.0;
+        if constexpr (PC) accz[j] = 0.0;
+    }
     // the kMultiPadRows rows behind the end of P are what the product's last 16-byte vector of a row meets past column n (against
     // zeros of the row padding): zero in THIS instantiation's layout, whatever another K left there
     if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) P[n * K + threadIdx.x] = (TV)0;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        [[maybe_unused]] TV di;
+        if constexpr (PC) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
             const TV bi = B[i * K + j];
             X[i * K + j] = (TV)0;
             R[i * K + j] = bi;
-            P[i * K + j] = bi;
+            if constexpr (PC) {
+                const TV zi = di * bi;
+                P[i * K + j] = zi;
+                accz[j] += (double)bi * (double)zi;
+            } else {
+                P[i * K + j] = bi;
+            }
             acc[j] += (double)bi * (double)bi;
         }
     }
 #pragma unroll
     for (int j = 0; j < K; j++) {
         const double t = block_sum(acc[j], s_red);
-        if (threadIdx.x == 0) partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+        [[maybe_unused]] double tz;
+        if constexpr (PC) tz = block_sum(accz[j], s_red);
+        if (threadIdx.x == 0) {
+            partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            if constexpr (PC) partial_rz[(size_t)j * gridDim.x + blockIdx.x] = tz;
+        }
     }
 }
 
-// per column: bb = rr[0] = sum of its partials, iters = 0; live columns start running, padding columns are born stopped
-template <int K>
+// per column: bb = rr[0] = sum of its partials (PC: rz[0] = the sum of its r.z partials), iters = 0; live columns start running,
+// padding columns are born stopped
+template <int K, bool PC>
 __global__ void __launch_bounds__(kBlock)
-multi_init_scalars_kernel(const double *__restrict__ red, int nred, int nrhs, MultiScalars *sc, volatile int *host_flags)
+multi_init_scalars_kernel(const double *__restrict__ red, int nred, int nrhs, BatchScalars *sc, volatile int *host_flags,
+                          const double *__restrict__ red_rz)
 {
     __shared__ double s_red[kWaves];
     for (int j = 0; j < kMaxRhs; j++) {
         const double t = j < K ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        [[maybe_unused]] double tz;
+        if constexpr (PC) tz = j < K ? block_sum_array(red_rz + (size_t)j * nred, nred, s_red) : 0.0;
         if (threadIdx.x == 0) {
             CgScalars &c = sc->col[j];
             c.bb = t; c.rr[0] = t; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
             c.stop = j < nrhs ? 0 : 1;
+            if constexpr (PC) { sc->rz[j][0] = tz; sc->rz[j][1] = 0.0; }
         }
     }
     if (threadIdx.x == 0) {
@@ -2645,27 +2683,34 @@ multi_init_scalars_kernel(const double *__restrict__ red, int nred, int nrhs, Mu
     }
 }
 
-// per live, running column j: alpha_j = rr_j / p_j.Ap_j ; x_j += alpha_j p_j ; r_j -= alpha_j Ap_j ; partials of r_j.r_j
+// per live, running column j: alpha_j = rr_j / p_j.Ap_j (PC: rz_j / p_j.Ap_j) ; x_j += alpha_j p_j ; r_j -= alpha_j Ap_j ; partials
+// of r_j.r_j (PC: and of r_j.(dinv o r_j))
 // (update_xr_kernel's statements, column by column; a stopped column is not read and not written)
-template <typename TV, int K>
+template <typename TV, int K, bool PC>
 __global__ void __launch_bounds__(kBlock)
-multi_xr_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k, const TV *__restrict__ P,
-                const TV *__restrict__ AP, TV *__restrict__ X, TV *__restrict__ R, uint64_t n, double *__restrict__ partial)
+multi_xr_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int k, const TV *__restrict__ P, const TV *__restrict__ AP,
+                TV *__restrict__ X, TV *__restrict__ R, uint64_t n, double *__restrict__ partial, const TV *__restrict__ dinv,
+                double *__restrict__ partial_rz)
 {
     __shared__ double s_red[kWaves];
     if (sc->all_stop) return;
     bool run[K];
     double alpha_d[K], pAp[K], acc[K];
+    [[maybe_unused]] double accz[K];
     TV alpha[K];
 #pragma unroll
     for (int j = 0; j < K; j++) {
         run[j] = sc->col[j].stop == 0;
         pAp[j] = block_sum_array(red + (size_t)j * nred, nred, s_red);
-        alpha_d[j] = sc->col[j].rr[(k + 1) & 1] / pAp[j];
+        if constexpr (PC) alpha_d[j] = sc->rz[j][(k + 1) & 1] / pAp[j];
+        else alpha_d[j] = sc->col[j].rr[(k + 1) & 1] / pAp[j];
         alpha[j] = (TV)alpha_d[j];
         acc[j] = 0.0;
+        if constexpr (PC) accz[j] = 0.0;
     }
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        [[maybe_unused]] TV di;
+        if constexpr (PC) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
             if (!run[j]) continue;
@@ -2674,26 +2719,37 @@ multi_xr_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int 
             const TV ri = -alpha[j] * AP[e] + R[e];
             R[e] = ri;
             acc[j] += (double)ri * (double)ri;
+            if constexpr (PC) {
+                const TV zi = di * ri;
+                accz[j] += (double)ri * (double)zi;
+            }
         }
     }
 #pragma unroll
     for (int j = 0; j < K; j++) {
         const double t = block_sum(acc[j], s_red);
+        [[maybe_unused]] double tz;
+        if constexpr (PC) tz = block_sum(accz[j], s_red);
         if (threadIdx.x == 0) {
             partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            if constexpr (PC) partial_rz[(size_t)j * gridDim.x + blockIdx.x] = tz;
             if (blockIdx.x == 0 && run[j]) { sc->col[j].pAp = pAp[j]; sc->col[j].alpha = alpha_d[j]; }
         }
     }
 }
 
-// per running column j: rr' = r_j.r_j ; beta = rr'/rr ; if sqrt(rr'/bb_j) < tol the column stops (p_j untouched, its scalars are
-// final) else p_j = r_j + beta p_j.  The progress word reports the iteration, and "stopped" once EVERY live column has stopped.
+// per running column j: rr' = r_j.r_j (PC: rz' = r_j.z_j) ; beta = rr'/rr (PC: rz'/rz) ; if sqrt(rr'/bb_j) < tol the column stops
+// (p_j untouched, its scalars are final) else p_j = r_j + beta p_j (PC: dinv o r_j + beta p_j).  The progress word reports the
+// iteration, and "stopped" once EVERY live column has stopped.
 // Workgroup 0 is the only writer of the scalars; a workgroup that starts after it has raised a column's stop flag sees that column
 // as stopped and leaves p_j alone, which is what it would have decided itself from the same bits (update_p_kernel's argument).
-template <typename TV, int K>
+// The PC p statement is an explicit fma(beta, p, z) with z = dinv o r rounded on its own: the plain r + beta p contracts to
+// fma(beta, p, r), and z must not be the operand that is fused (fma(dinv, r, beta p) rounds differently).
+template <typename TV, int K, bool PC>
 __global__ void __launch_bounds__(kBlock)
-multi_p_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k, double rel_error, const TV *__restrict__ R,
-               TV *__restrict__ P, uint64_t n, volatile int *host_flags)
+multi_p_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int k, double rel_error, const TV *__restrict__ R,
+               TV *__restrict__ P, uint64_t n, volatile int *host_flags, const TV *__restrict__ dinv,
+               const double *__restrict__ red_rz)
 {
     __shared__ double s_red[kWaves];
     if (sc->all_stop) return;
@@ -2704,9 +2760,15 @@ multi_p_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k
     for (int j = 0; j < K; j++) {
         const bool run = sc->col[j].stop == 0;
         const double rr_new = block_sum_array(red + (size_t)j * nred, nred, s_red);
-        const double rr = sc->col[j].rr[(k + 1) & 1];
+        [[maybe_unused]] double rz_new;
+        if constexpr (PC) rz_new = block_sum_array(red_rz + (size_t)j * nred, nred, s_red);
+        double rho;                              // what beta divides by: the previous r.r (PC: r.z)
+        if constexpr (PC) rho = sc->rz[j][(k + 1) & 1];
+        else rho = sc->col[j].rr[(k + 1) & 1];
         const double bb = sc->col[j].bb;
-        const double beta_d = rr_new / rr;
+        double beta_d;
+        if constexpr (PC) beta_d = rz_new / rho;
+        else beta_d = rr_new / rho;
         const bool stop = sqrt(rr_new / bb) < rel_error;
         upd[j] = run && !stop;
         beta[j] = (TV)beta_d;
@@ -2714,6 +2776,7 @@ multi_p_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k
         if (run && blockIdx.x == 0 && threadIdx.x == 0) {
             CgScalars &c = sc->col[j];
             c.rr[k & 1] = rr_new;
+            if constexpr (PC) sc->rz[j][k & 1] = rz_new;
             c.beta = beta_d;
             c.iters = k;
         }
@@ -2732,11 +2795,18 @@ multi_p_kernel(const double *__restrict__ red, int nred, MultiScalars *sc, int k
     }
     if (all) return;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        [[maybe_unused]] TV di;
+        if constexpr (PC) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
             if (!upd[j]) continue;
             const uint64_t e = i * K + j;
-            P[e] = R[e] + beta[j] * P[e];
+            if constexpr (PC) {
+                const TV zi = di * R[e];
+                P[e] = fma_tv(beta[j], P[e], zi);
+            } else {
+                P[e] = R[e] + beta[j] * P[e];
+            }
         }
     }
 }
@@ -2763,21 +2833,8 @@ multi_deinterleave_kernel(const TV *__restrict__ inter, int ncols, TV *__restric
 
 
 // ---------------------------------------------------------------------------------------------
-// Jacobi-preconditioned batched CG (lam_hip_solve_many_pc, lam_multi.h): the recurrences above with M = diag(A).
-// No reference counterpart: the reference is un-preconditioned.
-//   x = 0, r = b, p = z = dinv o b, rz = r.z ;  alpha = rz / p.Ap ; x += alpha p ; r -= alpha Ap ; rr' = r.r ; rz' = r.(dinv o r) ;
-//   stop test on sqrt(rr'/bb) as in the plain recurrence ; beta = rz'/rz ; p = dinv o r + beta p
-// Still three launches per iteration: the UNCHANGED multi_gemv_kernel, pcg_xr_kernel, pcg_p_kernel.  z is never stored: dinv (one
-// vector of n elements shared by the K columns, read once per row) is applied where z is needed.  The kernels are the plain ones
-// statement for statement (same reduction building blocks in the same order, partials at [j * grid + block]) with a second set of
-// partials for r.z, so on a matrix whose diagonal is a constant power of two every quantity is the plain recurrence's times an
-// exact power of two and x, the iteration counts and rel_err agree bit for bit.
+// The diagonal of the matrix: lam_hip_get_diagonal, and dinv of the preconditioned batch (PC above).
 // ---------------------------------------------------------------------------------------------
-struct PcgScalars {
-    MultiScalars m;               // what the plain batch keeps, with the same meaning (alpha, beta are the preconditioned ones)
-    double rz[kMaxRhs][2];        // r_j.z_j, ping-pong like CgScalars::rr: iteration k reads [(k+1)&1], writes [k&1]
-};
-
 // what the extraction found wrong with the diagonal: rows whose A_ii or 1/A_ii is not finite and > 0
 struct DiagInfo {
     unsigned long long first_bad; // smallest such GLOBAL row (~0: none)
@@ -2801,169 +2858,6 @@ diag_extract_kernel(const TA *__restrict__ A, uint64_t lda, uint64_t row0, uint6
         if (!ok && info != nullptr) {
             atomicMin(&info->first_bad, (unsigned long long)(row0 + i));
             atomicAdd(&info->count, 1ull);
-        }
-    }
-}
-
-// X = 0, R = B, P = dinv o B; per-workgroup partials of b_j.b_j and of r_j.z_j = b_j.(dinv o b_j), both at [j * gridDim.x + block]
-template <typename TV, int K>
-__global__ void __launch_bounds__(kBlock)
-pcg_init_kernel(const TV *__restrict__ B, const TV *__restrict__ dinv, TV *__restrict__ X, TV *__restrict__ R, TV *__restrict__ P,
-                uint64_t n, double *__restrict__ partial_bb, double *__restrict__ partial_rz)
-{
-    __shared__ double s_red[kWaves];
-    double acc[K], accz[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) acc[j] = accz[j] = 0.0;
-    if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) P[n * K + threadIdx.x] = (TV)0;       // see multi_init_kernel
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const TV di = dinv[i];
-#pragma unroll
-        for (int j = 0; j < K; j++) {
-            const TV bi = B[i * K + j];
-            const TV zi = di * bi;
-            X[i * K + j] = (TV)0;
-            R[i * K + j] = bi;
-            P[i * K + j] = zi;
-            acc[j] += (double)bi * (double)bi;
-            accz[j] += (double)bi * (double)zi;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        const double t = block_sum(acc[j], s_red);
-        const double tz = block_sum(accz[j], s_red);
-        if (threadIdx.x == 0) {
-            partial_bb[(size_t)j * gridDim.x + blockIdx.x] = t;
-            partial_rz[(size_t)j * gridDim.x + blockIdx.x] = tz;
-        }
-    }
-}
-
-// multi_init_scalars_kernel, plus rz[j][0] = the sum of column j's r.z partials
-template <int K>
-__global__ void __launch_bounds__(kBlock)
-pcg_init_scalars_kernel(const double *__restrict__ red_bb, const double *__restrict__ red_rz, int nred, int nrhs, PcgScalars *ps,
-                        volatile int *host_flags)
-{
-    __shared__ double s_red[kWaves];
-    for (int j = 0; j < kMaxRhs; j++) {
-        const double t = j < K ? block_sum_array(red_bb + (size_t)j * nred, nred, s_red) : 0.0;
-        const double tz = j < K ? block_sum_array(red_rz + (size_t)j * nred, nred, s_red) : 0.0;
-        if (threadIdx.x == 0) {
-            CgScalars &c = ps->m.col[j];
-            c.bb = t; c.rr[0] = t; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
-            c.stop = j < nrhs ? 0 : 1;
-            ps->rz[j][0] = tz; ps->rz[j][1] = 0.0;
-        }
-    }
-    if (threadIdx.x == 0) {
-        ps->m.all_stop = 0;
-        ps->m.pad = 0;
-        post_progress(host_flags, 0, false);
-    }
-}
-
-// per live, running column j: alpha_j = rz_j / p_j.Ap_j ; x_j += alpha_j p_j ; r_j -= alpha_j Ap_j ; partials of r_j.r_j and of
-// r_j.(dinv o r_j)  (multi_xr_kernel's statements; a stopped column is not read and not written)
-template <typename TV, int K>
-__global__ void __launch_bounds__(kBlock)
-pcg_xr_kernel(const double *__restrict__ red, int nred, PcgScalars *ps, int k, const TV *__restrict__ P, const TV *__restrict__ AP,
-              const TV *__restrict__ dinv, TV *__restrict__ X, TV *__restrict__ R, uint64_t n, double *__restrict__ partial_rr,
-              double *__restrict__ partial_rz)
-{
-    __shared__ double s_red[kWaves];
-    if (ps->m.all_stop) return;
-    bool run[K];
-    double alpha_d[K], pAp[K], acc[K], accz[K];
-    TV alpha[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        run[j] = ps->m.col[j].stop == 0;
-        pAp[j] = block_sum_array(red + (size_t)j * nred, nred, s_red);
-        alpha_d[j] = ps->rz[j][(k + 1) & 1] / pAp[j];
-        alpha[j] = (TV)alpha_d[j];
-        acc[j] = accz[j] = 0.0;
-    }
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const TV di = dinv[i];
-#pragma unroll
-        for (int j = 0; j < K; j++) {
-            if (!run[j]) continue;
-            const uint64_t e = i * K + j;
-            X[e] = alpha[j] * P[e] + X[e];
-            const TV ri = -alpha[j] * AP[e] + R[e];
-            R[e] = ri;
-            const TV zi = di * ri;
-            acc[j] += (double)ri * (double)ri;
-            accz[j] += (double)ri * (double)zi;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        const double t = block_sum(acc[j], s_red);
-        const double tz = block_sum(accz[j], s_red);
-        if (threadIdx.x == 0) {
-            partial_rr[(size_t)j * gridDim.x + blockIdx.x] = t;
-            partial_rz[(size_t)j * gridDim.x + blockIdx.x] = tz;
-            if (blockIdx.x == 0 && run[j]) { ps->m.col[j].pAp = pAp[j]; ps->m.col[j].alpha = alpha_d[j]; }
-        }
-    }
-}
-
-// per running column j: rr' = r_j.r_j ; rz' = r_j.z_j ; if sqrt(rr'/bb_j) < tol the column stops (p_j untouched, its scalars are
-// final) else beta = rz'/rz ; p_j = dinv o r_j + beta p_j.  Progress word, all_stop and the single-writer argument: multi_p_kernel.
-// The p statement is an explicit fma(beta, p, z) with z = dinv o r rounded on its own: the plain kernel's r + beta p contracts to
-// fma(beta, p, r), and z must not be the operand that is fused (fma(dinv, r, beta p) rounds differently).
-template <typename TV, int K>
-__global__ void __launch_bounds__(kBlock)
-pcg_p_kernel(const double *__restrict__ red_rr, const double *__restrict__ red_rz, int nred, PcgScalars *ps, int k, double rel_error,
-             const TV *__restrict__ R, const TV *__restrict__ dinv, TV *__restrict__ P, uint64_t n, volatile int *host_flags)
-{
-    __shared__ double s_red[kWaves];
-    if (ps->m.all_stop) return;
-    bool upd[K];
-    TV beta[K];
-    bool all = true;
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        const bool run = ps->m.col[j].stop == 0;
-        const double rr_new = block_sum_array(red_rr + (size_t)j * nred, nred, s_red);
-        const double rz_new = block_sum_array(red_rz + (size_t)j * nred, nred, s_red);
-        const double rz = ps->rz[j][(k + 1) & 1];
-        const double bb = ps->m.col[j].bb;
-        const double beta_d = rz_new / rz;
-        const bool stop = sqrt(rr_new / bb) < rel_error;
-        upd[j] = run && !stop;
-        beta[j] = (TV)beta_d;
-        all = all && !upd[j];
-        if (run && blockIdx.x == 0 && threadIdx.x == 0) {
-            CgScalars &c = ps->m.col[j];
-            c.rr[k & 1] = rr_new;
-            ps->rz[j][k & 1] = rz_new;
-            c.beta = beta_d;
-            c.iters = k;
-        }
-    }
-    if (blockIdx.x == 0) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int j = 0; j < K; j++)
-                if (!upd[j]) ps->m.col[j].stop = 1;
-            if (all) ps->m.all_stop = 1;
-            post_progress(host_flags, k, all);
-        }
-    }
-    if (all) return;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const TV di = dinv[i];
-#pragma unroll
-        for (int j = 0; j < K; j++) {
-            if (!upd[j]) continue;
-            const uint64_t e = i * K + j;
-            const TV zi = di * R[e];
-            P[e] = fma_tv(beta[j], P[e], zi);
         }
     }
 }

@@ -8,6 +8,8 @@
 // (fp64: 4096 / 2048 / 1024 / 512 columns for K = 1 / 2 / 4 / 8; fp32: 4096 / 4096 / 2048 / 1024), non-temporal matrix loads.
 // Three launches per iteration (product; x, r; p), all on shard 0's stream; the host follows the batch's own pinned progress word
 // with the lag rule of the single solve (lag_check), where "stopped" means every live column has stopped.
+// One recurrence in the source: lam_hip_solve_many_pc(JACOBI) runs the PC = true instantiations of the same four vector kernels
+// (multi_init_kernel, multi_init_scalars_kernel, multi_xr_kernel, multi_p_kernel) on the same scalars' block.
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
@@ -17,17 +19,20 @@ namespace {
 constexpr int kMultiRows = 4;     // rows per workgroup of multi_gemv_kernel
 constexpr int kMultiWaves = 4;    // waves per workgroup
 
+void free_dev(std::initializer_list<void *> ptrs)
+{
+    for (void *q : ptrs) if (q) (void)hipFree(q);
+}
+
 void multi_release(lam_hip_ctx *c)
 {
     MultiState &m = c->multi;
     if (m.n == 0) return;        // the preconditioner's state is allocated behind the batch's only (pcg_ensure)
     if (c->sh.empty() || hipSetDevice(c->sh[0].dev) != hipSuccess) { (void)hipGetLastError(); return; }
     if (c->sh[0].stream) (void)hipStreamSynchronize(c->sh[0].stream);
-    void *pdev[] = {c->pcg.diag, c->pcg.dinv, c->pcg.part_rz, c->pcg.sc, c->pcg.info};
-    for (void *q : pdev) if (q) (void)hipFree(q);
+    free_dev({c->pcg.diag, c->pcg.dinv, c->pcg.part_rz, c->pcg.info});
     c->pcg = PcgState();
-    void *dev[] = {m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.sc};
-    for (void *q : dev) if (q) (void)hipFree(q);
+    free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -68,7 +73,7 @@ int multi_ensure(lam_hip_ctx *c)
     for (auto v : vecs) HIPCHK(c, hipMalloc(v, elems * ev));
     HIPCHK(c, hipMalloc((void **)&m.part_gemv, sizeof(double) * kMaxRhs * (size_t)c->n));
     HIPCHK(c, hipMalloc((void **)&m.part_vec, sizeof(double) * kMaxRhs * kVecBlocksMax));
-    HIPCHK(c, hipMalloc((void **)&m.sc, sizeof(MultiScalars)));
+    HIPCHK(c, hipMalloc((void **)&m.sc, sizeof(BatchScalars)));
     HIPCHK(c, hipHostMalloc((void **)&m.sc_host, sizeof(MultiScalars), hipHostMallocDefault));
     HIPCHK(c, hipHostMalloc((void **)&m.host_flags, 64, hipHostMallocDefault));
     m.host_flags[0] = m.host_flags[1] = 0;
@@ -80,7 +85,7 @@ int multi_ensure(lam_hip_ctx *c)
     // the product reads whole 16-byte vectors of a row: up to 7 columns behind the end of P are met (by zeros of the row padding),
     // so P is zero behind row n and stays so -- the kernels write rows below n only
     HIPCHK(c, hipMemsetAsync(m.P, 0, elems * ev, s.stream));
-    HIPCHK(c, hipMemsetAsync(m.sc, 0, sizeof(MultiScalars), s.stream));
+    HIPCHK(c, hipMemsetAsync(m.sc, 0, sizeof(BatchScalars), s.stream));
     HIPCHK(c, hipStreamSynchronize(s.stream));
     return 0;
 }
@@ -103,6 +108,12 @@ int multi_dispatch(lam_hip_ctx *c, int K, F &&f)
     if (c->dtype == LAM_HIP_F64) return multi_dispatch_k(c, K, [&](auto k) -> int { return f(Impl<double, double>(), k); });
     if (c->dtype == LAM_HIP_F32) return multi_dispatch_k(c, K, [&](auto k) -> int { return f(Impl<float, float>(), k); });
     return fail(c, LAM_HIP_EINVAL, "the multi-right-hand-side path has no kernels for dtype %d", c->dtype);
+}
+// the recurrence's: f(Impl<TA, TV>(), integral_constant<int, K>(), bool_constant<PC>()), PC = Jacobi-preconditioned
+template <typename F>
+int multi_dispatch(lam_hip_ctx *c, int K, bool pc, F &&f)
+{
+    return multi_dispatch(c, K, [&](auto impl, auto k) -> int { return pc ? f(impl, k, std::true_type()) : f(impl, k, std::false_type()); });
 }
 
 int multi_gemv_grid(const lam_hip_ctx *c) { return (int)((c->n + kMultiRows - 1) / kMultiRows); }
@@ -153,23 +164,18 @@ int multi_download(lam_hip_ctx *c, int nrhs, int K, const void *src, void *host)
 }
 
 // The Jacobi preconditioner of lam_hip_solve_many_pc.  No reference counterpart: the reference is un-preconditioned.
+// Sized for the batch's n (multi_solve has checked multi.n == n) and released with the batch, so "allocated" is all there is to know.
 int pcg_ensure(lam_hip_ctx *c)
 {
     PcgState &g = c->pcg;
-    if (g.n == c->n) return 0;
-    ShardBase &s = c->sh[0];
-    LAMCHK(set_dev(c, s));
-    void *old[] = {g.diag, g.dinv, g.part_rz, g.sc, g.info};
-    for (void *q : old) if (q) (void)hipFree(q);
-    g = PcgState();              // g.n == 0 until everything below has succeeded: a failure is retried, never launched on
+    if (g.info) return 0;
+    LAMCHK(set_dev(c, c->sh[0]));
+    free_dev({g.diag, g.dinv, g.part_rz});      // what a failed attempt left: it is retried, never launched on
+    g = PcgState();
     HIPCHK(c, hipMalloc(&g.diag, c->n * c->esz_v()));
     HIPCHK(c, hipMalloc(&g.dinv, c->n * c->esz_v()));
     HIPCHK(c, hipMalloc((void **)&g.part_rz, sizeof(double) * kMaxRhs * kVecBlocksMax));
-    HIPCHK(c, hipMalloc((void **)&g.sc, sizeof(PcgScalars)));
     HIPCHK(c, hipMalloc((void **)&g.info, sizeof(DiagInfo)));
-    HIPCHK(c, hipMemsetAsync(g.sc, 0, sizeof(PcgScalars), s.stream));
-    HIPCHK(c, hipStreamSynchronize(s.stream));
-    g.n = c->n;
     return 0;
 }
 
@@ -245,10 +251,10 @@ int lam_hip_set_rhs_many(lam_hip_ctx *c, int nrhs, const void *b_host)
 
 namespace {
 
-// lam_hip_solve_many (precond = LAM_HIP_PC_NONE) and lam_hip_solve_many_pc: one body.  The plain batch launches exactly what it
-// always did; the Jacobi-preconditioned one swaps the two vector kernels and the initialisation for their pcg_* counterparts and
-// keeps its scalars in PcgState (the plain batch's device scalars are not touched), the product launch, the progress word, the
-// lag rule and the per-column results are shared.
+// lam_hip_solve_many (precond = LAM_HIP_PC_NONE) and lam_hip_solve_many_pc: one body, one sequence of launches.  The
+// Jacobi-preconditioned batch runs the PC = true instantiations of the four vector kernels on dinv and a second partial array (both
+// null for the plain batch); the product launch, the scalars' block, the progress word, the lag rule and the per-column results are
+// shared.
 int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters,
                 int32_t *converged, double *rel_err)
 {
@@ -273,7 +279,6 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, doub
             return fail(c, LAM_HIP_EINVAL, "%s: the Jacobi preconditioner needs A[i][i] and 1/A[i][i] finite and > 0: row %llu holds %g "
                         "(%llu such rows)", fn, (unsigned long long)g.bad_row, g.bad_value, (unsigned long long)g.bad_count);
     }
-    MultiScalars *const sc_dev = pc ? &g.sc->m : m.sc;
     m.host_flags[0] = m.host_flags[1] = 0;
     for (int i = 0; i < kLag; i++) m.timed_slot[i] = false;
     c->prog_t = 0.0;
@@ -284,28 +289,21 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, doub
     const int vb = vec_grid(c->n), gb = multi_gemv_grid(c);
     double gemv_ms = 0.0;
     int samples = 0, enq = 0;
-    LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc) -> int {
+    LAMCHK(multi_dispatch(c, m.K, pc, [&](auto impl, auto kc, auto pct) -> int {
         using I = decltype(impl);
         using TA = typename ImplTraits<I>::TA;
         using TV = typename ImplTraits<I>::TV;
         constexpr int K = decltype(kc)::value;
-        if (!pc) {
-            // x = 0, r = p = b, bb_j = b_j.b_j
-            hipLaunchKernelGGL((multi_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X, (TV *)m.R,
-                               (TV *)m.P, c->n, m.part_vec);
-            HIPCHK(c, hipGetLastError());
-            hipLaunchKernelGGL((multi_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs,
-                               m.sc, (volatile int *)m.host_flags);
-            HIPCHK(c, hipGetLastError());
-        } else {
-            // x = 0, r = b, p = dinv o b, bb_j = b_j.b_j, rz_j = b_j.(dinv o b_j)
-            hipLaunchKernelGGL((pcg_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (const TV *)g.dinv, (TV *)m.X,
-                               (TV *)m.R, (TV *)m.P, c->n, m.part_vec, g.part_rz);
-            HIPCHK(c, hipGetLastError());
-            hipLaunchKernelGGL((pcg_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec,
-                               (const double *)g.part_rz, vb, m.nrhs, g.sc, (volatile int *)m.host_flags);
-            HIPCHK(c, hipGetLastError());
-        }
+        constexpr bool PC = decltype(pct)::value;
+        const TV *const dinv = PC ? (const TV *)g.dinv : nullptr;
+        double *const part_rz = PC ? g.part_rz : nullptr;
+        // x = 0, r = b, p = b, bb_j = b_j.b_j  (PC: p = dinv o b, rz_j = b_j.(dinv o b_j))
+        hipLaunchKernelGGL((multi_init_kernel<TV, K, PC>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X, (TV *)m.R,
+                           (TV *)m.P, c->n, m.part_vec, dinv, part_rz);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((multi_init_scalars_kernel<K, PC>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs,
+                           m.sc, (volatile int *)m.host_flags, (const double *)part_rz);
+        HIPCHK(c, hipGetLastError());
         for (int i = 0; i < max_iters; i++) {
             const int k = i + 1, slot = i % kLag;
             if (i >= kLag) {
@@ -318,24 +316,14 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, doub
             const bool timed = timed_iteration(c, s0, k);
             m.timed_slot[slot] = timed;
             if (timed) RECORD(c, m.ev0[slot], s0.stream);
-            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, sc_dev)));
+            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, m.sc)));
             if (timed) RECORD(c, m.ev1[slot], s0.stream);
-            if (!pc) {
-                hipLaunchKernelGGL((multi_xr_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
-                                   (const TV *)m.P, (const TV *)m.AP, (TV *)m.X, (TV *)m.R, c->n, m.part_vec);
-                LAUNCHED(c);
-                hipLaunchKernelGGL((multi_p_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k,
-                                   rel_error, (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags);
-                LAUNCHED(c);
-            } else {
-                hipLaunchKernelGGL((pcg_xr_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, g.sc, k,
-                                   (const TV *)m.P, (const TV *)m.AP, (const TV *)g.dinv, (TV *)m.X, (TV *)m.R, c->n, m.part_vec, g.part_rz);
-                LAUNCHED(c);
-                hipLaunchKernelGGL((pcg_p_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec,
-                                   (const double *)g.part_rz, vb, g.sc, k, rel_error, (const TV *)m.R, (const TV *)g.dinv, (TV *)m.P, c->n,
-                                   (volatile int *)m.host_flags);
-                LAUNCHED(c);
-            }
+            hipLaunchKernelGGL((multi_xr_kernel<TV, K, PC>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
+                               (const TV *)m.P, (const TV *)m.AP, (TV *)m.X, (TV *)m.R, c->n, m.part_vec, dinv, part_rz);
+            LAUNCHED(c);
+            hipLaunchKernelGGL((multi_p_kernel<TV, K, PC>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k,
+                               rel_error, (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags, dinv, (const double *)part_rz);
+            LAUNCHED(c);
             c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
             enq++;
         }
@@ -347,7 +335,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, doub
     }
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     for (int j = 0; j < kLag; j++) multi_harvest(m, j, &gemv_ms, &samples);
-    HIPCHK(c, hipMemcpyAsync(m.sc_host, sc_dev, sizeof(MultiScalars), hipMemcpyDeviceToHost, s0.stream));
+    HIPCHK(c, hipMemcpyAsync(m.sc_host, m.sc, sizeof(MultiScalars), hipMemcpyDeviceToHost, s0.stream));
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     m.solved = true;
     const double t1 = now_s();

@@ -102,7 +102,7 @@ def first_cg_step(b, Ab, vec_dtype):
 
 
 def first_pcg_step(b, d, Az, vec_dtype):
-    """The first Jacobi-preconditioned step from x = 0 as pcg_init_kernel / pcg_xr_kernel compute it, for integer b, a power-of-two
+    """The first Jacobi-preconditioned step from x = 0 as multi_init_kernel / multi_xr_kernel compute it with PC = true, for integer b, a power-of-two
     diagonal d and Az = A z0 with z0 = b / d (exact):  alpha = fl64(r.z / p.Ap) with r.z = sum b_i z0_i and p.Ap = sum z0_i (A z0)_i
     both exact, rounded once to the vector type, x1 = fl(alpha_TV * z0).  Returns (alpha_TV, x1, bb, r1) with bb = b.b and
     r1 = b - alpha_TV A z0 in fp64."""

@@ -4,7 +4,7 @@ de-interleave pair (csrc/lam_kernels.h) through lam_hip_solve_many / _solve_many
 A. Jacobi with a NON-constant diagonal, bit for bit.  C is symmetric positive definite with a unit diagonal (the smoke system
    divided by sqrt(d_i d_j), tests/pcg_reference.py), S = diag(2^e_i) with integer e_i in [-6, 6] that differ between neighbouring
    rows, A = S C S.  Every product, partial sum and scalar of the Jacobi run on (A, S b) is the plain run's on (C, b) times an exact
-   power of two (pcg_p_kernel's comment makes the contraction argument), so x_jacobi[i] = 2^-e_i x_plain[i] BIT FOR BIT for every
+   power of two (multi_p_kernel's comment makes the contraction argument), so x_jacobi[i] = 2^-e_i x_plain[i] BIT FOR BIT for every
    column and every iteration count; a wrong index into dinv anywhere breaks it in the rows it touches.  tests/test_pcg_cpu.py
    holds the same identity on the numpy restatement.  rel_err of the plain run stays above 1e-30 (nothing underflows, no 0/0);
    where the cap is k = n the last step annihilates the residual (exactly, for n = 1: C = [1], alpha = 1, r = b - b), so there the
