@@ -277,18 +277,21 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
     // Several right-hand sides on the matrix already held (lam_hip_solve_many: independent CG recurrences, one pass over the matrix
     // per iteration; one shard, double / float).  B: nrhs vectors of get_num_cols() elements, vector j at B + j * cols; X (may be
     // null): the solutions in the same layout; num_iters / converged / rel_err (may be null): nrhs entries each.  stats() then
-    // describes the batch.  Returns true iff every column converged.  No reference counterpart (its drivers are run once per rhs
+    // describes the batch.  Returns true iff every column converged; batch_failed() tells a call that returned an error from one
+    // that merely did not converge.  No reference counterpart (its drivers are run once per rhs
     // file).  Not virtual on purpose: a member of a class template is instantiated only where it is called, so programs that do
     // not use it link against an ABI without the batched entry points.
     bool solve_many(int nrhs, const FloatingType *B, FloatingType *X, int max_iters, FloatingType rel_error, int32_t *num_iters = nullptr,
                     int32_t *converged = nullptr, double *rel_err = nullptr)
     {
+        _batch_failed = true;
         if (!ensure_ctx()) return false;
         if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
         lam_hip_stats st;
         if (lam_hip_solve_many(_ctx, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0) return report("solve_many");
         _stats = st;
         if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        _batch_failed = false;
         return st.converged != 0;
     }
     // solve_many with a preconditioner (lam_hip_solve_many_pc): precond = LAM_HIP_PC_NONE is solve_many itself, LAM_HIP_PC_JACOBI
@@ -298,6 +301,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
     bool solve_many_pc(int precond, int nrhs, const FloatingType *B, FloatingType *X, int max_iters, FloatingType rel_error,
                        int32_t *num_iters = nullptr, int32_t *converged = nullptr, double *rel_err = nullptr)
     {
+        _batch_failed = true;
         if (!ensure_ctx()) return false;
         if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
         lam_hip_stats st;
@@ -305,7 +309,37 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
             return report("solve_many_pc");
         _stats = st;
         if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        _batch_failed = false;
         return st.converged != 0;
+    }
+    // solve_many_pc from an initial guess (lam_hip_solve_many_x0).  X0: nrhs guesses laid out as B; null = from the batch's current
+    // solution, the restart or continuation of the last solve_many* call.  B may be null: the right-hand sides already set stay
+    // (a new lam_hip_set_rhs_many would void the solution a continuation starts from, so X0 == null needs B == null).  A guess
+    // that already meets rel_error gives 0 iterations, which is an answer and not a failure: batch_failed() tells the two apart.
+    bool solve_many_x0(int precond, int nrhs, const FloatingType *B, const FloatingType *X0, FloatingType *X, int max_iters,
+                       FloatingType rel_error, int32_t *num_iters = nullptr, int32_t *converged = nullptr, double *rel_err = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (B != nullptr && lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        lam_hip_stats st;
+        if (lam_hip_solve_many_x0(_ctx, precond, X0, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0)
+            return report("solve_many_x0");
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        _batch_failed = false;
+        return st.converged != 0;
+    }
+    bool batch_failed() const { return _batch_failed; }      // the last solve_many* / true_residual_many call returned an error
+    // ||b_j - A x_j|| / ||b_j|| of the first nrhs columns of the last batched solution, one batched product
+    // (lam_hip_true_residual_many); the solution stays readable and continuable
+    bool true_residual_many(int nrhs, double *rel_res)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_true_residual_many(_ctx, nrhs, rel_res) != 0) return report("true_residual_many");
+        _batch_failed = false;
+        return true;
     }
 
     // rows held by this process (all of them in the single-process classes), like the reference getters
@@ -379,6 +413,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
     bool _comm_init_column = false;   // extra column of the NCCL variant
     bool _gemv_plus_comm = [] { const char *v = getenv("LAM_CSV_GEMV_PLUS_COMM"); return v && *v && *v != '0'; }();
     lam_hip_stats _stats{};
+    bool _batch_failed = false;
 };
 
 }  // namespace LAM

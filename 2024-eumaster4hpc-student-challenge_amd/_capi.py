@@ -128,6 +128,9 @@ def lib():
                                     C.POINTER(C.c_double)], i32),
             "lam_hip_solve_many_pc": ([vp, i32, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double)], i32),
+            "lam_hip_solve_many_x0": ([vp, i32, vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double)], i32),
+            "lam_hip_true_residual_many": ([vp, i32, C.POINTER(C.c_double)], i32),
             "lam_hip_get_diagonal": ([vp, vp], i32),
             "lam_hip_get_solution_many": ([vp, i32, vp], i32),
             "lam_hip_gemv_many": ([vp, i32, vp, vp], i32),
@@ -419,16 +422,27 @@ class Solver:
         self._chk(self._L.lam_hip_set_rhs_many(self._h, B.shape[0], B.ctypes.data_as(C.c_void_p)))
         self.nrhs = B.shape[0]
 
-    def solve_many(self, max_iters, rel_error, precond=PC_NONE):
+    def solve_many(self, max_iters, rel_error, precond=PC_NONE, x0=None):
         """Independent CG recurrences for the right-hand sides of set_rhs_many, one pass over the matrix per iteration.  Returns
         the per-column `converged` array; self.num_iters_many / converged_many / rel_err_many hold the per-column results and
-        self.stats the batch's.  precond: PC_NONE (lam_hip_solve_many) or PC_JACOBI (lam_hip_solve_many_pc, M = diag(A))."""
+        self.stats the batch's.  precond: PC_NONE (lam_hip_solve_many) or PC_JACOBI (lam_hip_solve_many_pc, M = diag(A)).
+        x0: None = from x = 0; an (nrhs, N) array = from that guess; "continue" = from the batch's current solution, the restart
+        or continuation of the last solve_many (both lam_hip_solve_many_x0)."""
         k = getattr(self, "nrhs", 0)
         ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
         st = Stats()
         out = (C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)), cv.ctypes.data_as(C.POINTER(C.c_int32)),
                re.ctypes.data_as(C.POINTER(C.c_double)))
-        if precond == PC_NONE:
+        if x0 is not None:
+            if isinstance(x0, str):
+                assert x0 == "continue", "x0 is None, an (nrhs, N) array or \"continue\""
+                guess = None
+            else:
+                X0 = self._as_columns(x0)
+                assert X0.shape[0] == k, "one guess per right-hand side of set_rhs_many"
+                guess = X0.ctypes.data_as(C.c_void_p)
+            self._chk(self._L.lam_hip_solve_many_x0(self._h, precond, guess, max_iters, rel_error, *out))
+        elif precond == PC_NONE:
             self._chk(self._L.lam_hip_solve_many(self._h, max_iters, rel_error, *out))
         else:
             self._chk(self._L.lam_hip_solve_many_pc(self._h, precond, max_iters, rel_error, *out))
@@ -441,6 +455,14 @@ class Solver:
         X = np.empty((self.nrhs, self.n), dtype=self.vec_dtype)
         self._chk(self._L.lam_hip_get_solution_many(self._h, self.nrhs, X.ctypes.data_as(C.c_void_p)))
         return X
+
+    def true_residuals(self, nrhs=None):
+        """||b_j - A x_j|| / ||b_j|| of the first nrhs (default: all) columns of the last solve_many, formed on the device with one
+        batched product (lam_hip_true_residual_many).  The solution stays readable and solve_many(x0="continue") continues from it."""
+        k = self.nrhs if nrhs is None else nrhs
+        r = np.zeros(max(k, 1), np.float64)
+        self._chk(self._L.lam_hip_true_residual_many(self._h, k, r.ctypes.data_as(C.POINTER(C.c_double))))
+        return r[:k].copy()
 
     def diagonal(self):
         """The stored diagonal of the matrix (N elements of the vector dtype), extracted on the device."""

@@ -93,6 +93,8 @@ struct MultiState {
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out
     double *part_gemv = nullptr; // [kMaxRhs][n]: p_j.Ap_j partials per product workgroup
     double *part_vec = nullptr;  // [kMaxRhs][kVecBlocksMax]
+    double *part_rr = nullptr;   // [kMaxRhs][kVecBlocksMax]: r0.r0 of a start from a guess, r.r of lam_hip_true_residual_many
+    double *res = nullptr;       // [kMaxRhs]: lam_hip_true_residual_many's quotients on their way to the host
     BatchScalars *sc = nullptr;  // device; every solve re-initialises it in its init launch
     MultiScalars *sc_host = nullptr;                  // pinned mirror of its MultiScalars prefix
     int *host_flags = nullptr;   // pinned progress word of the batch (post_progress)

@@ -104,11 +104,18 @@ __device__ __forceinline__ double block_sum_array(const double *__restrict__ src
 // polls it instead of waiting on an event per iteration (no marker packets between the iteration's kernels); one
 // word, so it can never see a new iteration count next to an old stop decision.  After a stop the later (no-op)
 // iterations return before writing, so the stopping iteration stays readable.
-__device__ __forceinline__ void post_progress(volatile int *host_flags, int k, bool stop)
+// post_progress_word writes the word itself -- the one place that knows its format -- and is called directly only for the one
+// report that is not an iteration's: a batch whose every column is born stopped (multi_init_scalars_kernel).
+__device__ __forceinline__ void post_progress_word(volatile int *host_flags, int iters, int stop_at)
 {
     if (host_flags == nullptr) return;
     *reinterpret_cast<volatile unsigned long long *>(host_flags) =
-        ((unsigned long long)(unsigned)(stop ? k : 0) << 32) | (unsigned long long)(unsigned)k;
+        ((unsigned long long)(unsigned)stop_at << 32) | (unsigned long long)(unsigned)iters;
+}
+
+__device__ __forceinline__ void post_progress(volatile int *host_flags, int k, bool stop)
+{
+    post_progress_word(host_flags, k, stop ? k : 0);
 }
 
 struct PtrList {                      // destinations of a replicated store (one per shard)
@@ -2610,19 +2617,26 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
 }
 
 // X = 0, R = B, P = B (PC: dinv o B); per-workgroup partials of b_j.b_j (PC: and of r_j.z_j = b_j.(dinv o b_j)), both at
-// [j * gridDim.x + block]
-template <typename TV, int K, bool PC>
+// [j * gridDim.x + block].
+// GUESS (lam_hip_solve_many_x0): the guess x0 is in P and AX holds A x0 (one batched product in front of this launch).  X = x0,
+// R = B - AX rounded to the vector dtype, P = R (PC: dinv o R); b_j.b_j still goes to `partial`, r_j.r_j to partial_rr and r_j.z_j
+// to partial_rz.  r.r and r.z are accumulated by the statements, and so in the order, that take b.b and b.(dinv o b) without a
+// guess: with x0 = 0 (AX = 0, R = B exactly) their sums are those sums, bit for bit.
+template <typename TV, int K, bool PC, bool GUESS>
 __global__ void __launch_bounds__(kBlock)
 multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__ R, TV *__restrict__ P, uint64_t n,
-                  double *__restrict__ partial, const TV *__restrict__ dinv, double *__restrict__ partial_rz)
+                  double *__restrict__ partial, const TV *__restrict__ dinv, double *__restrict__ partial_rz,
+                  const TV *__restrict__ AX, double *__restrict__ partial_rr)
 {
     __shared__ double s_red[kWaves];
     double acc[K];
     [[maybe_unused]] double accz[K];
+    [[maybe_unused]] double accb[K];
 #pragma unroll
     for (int j = 0; j < K; j++) {
         acc[j] = 0.0;
         if constexpr (PC) accz[j] = 0.0;
+        if constexpr (GUESS) accb[j] = 0.0;
     }
     // the kMultiPadRows rows behind the end of P are what the product's last 16-byte vector of a row meets past column n (against
     // zeros of the row padding): zero in THIS instantiation's layout, whatever another K left there
@@ -2632,8 +2646,14 @@ multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__
         if constexpr (PC) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            const TV bi = B[i * K + j];
-            X[i * K + j] = (TV)0;
+            TV bi = B[i * K + j];                // from here on r0's element: b's without a guess
+            if constexpr (GUESS) {
+                accb[j] += (double)bi * (double)bi;
+                X[i * K + j] = P[i * K + j];
+                bi = bi - AX[i * K + j];
+            } else {
+                X[i * K + j] = (TV)0;
+            }
             R[i * K + j] = bi;
             if constexpr (PC) {
                 const TV zi = di * bi;
@@ -2650,36 +2670,104 @@ multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__
         const double t = block_sum(acc[j], s_red);
         [[maybe_unused]] double tz;
         if constexpr (PC) tz = block_sum(accz[j], s_red);
+        [[maybe_unused]] double tb;
+        if constexpr (GUESS) tb = block_sum(accb[j], s_red);
         if (threadIdx.x == 0) {
-            partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            if constexpr (GUESS) {
+                partial[(size_t)j * gridDim.x + blockIdx.x] = tb;
+                partial_rr[(size_t)j * gridDim.x + blockIdx.x] = t;
+            } else {
+                partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            }
             if constexpr (PC) partial_rz[(size_t)j * gridDim.x + blockIdx.x] = tz;
         }
     }
 }
 
 // per column: bb = rr[0] = sum of its partials (PC: rz[0] = the sum of its r.z partials), iters = 0; live columns start running,
-// padding columns are born stopped
-template <int K, bool PC>
+// padding columns are born stopped.
+// GUESS: rr[0] is the sum of the r0.r0 partials (red_rr), and the stop test is taken at k = 0: a live column whose guess already
+// meets sqrt(rr0/bb) < rel_error is born stopped -- 0 iterations, converged, x = x0 as it came -- instead of dividing 0 by 0 in
+// its first alpha.  If that is every live column the batch is over before its first iteration: all_stop is raised, the iteration's
+// launches return at once and never post, so the progress word itself says "stopped before iteration 1" (iteration 0, stop mark
+// 1: the smallest mark the lag rule acts on, at the host's first look).
+template <int K, bool PC, bool GUESS>
 __global__ void __launch_bounds__(kBlock)
 multi_init_scalars_kernel(const double *__restrict__ red, int nred, int nrhs, BatchScalars *sc, volatile int *host_flags,
-                          const double *__restrict__ red_rz)
+                          const double *__restrict__ red_rz, const double *__restrict__ red_rr, double rel_error)
 {
     __shared__ double s_red[kWaves];
+    [[maybe_unused]] bool all = true;
     for (int j = 0; j < kMaxRhs; j++) {
         const double t = j < K ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
         [[maybe_unused]] double tz;
         if constexpr (PC) tz = j < K ? block_sum_array(red_rz + (size_t)j * nred, nred, s_red) : 0.0;
+        double rr0 = t;
+        if constexpr (GUESS) rr0 = j < K ? block_sum_array(red_rr + (size_t)j * nred, nred, s_red) : 0.0;
+        bool born_stopped = j >= nrhs;
+        if constexpr (GUESS) {
+            born_stopped = born_stopped || sqrt(rr0 / t) < rel_error;
+            all = all && born_stopped;
+        }
         if (threadIdx.x == 0) {
             CgScalars &c = sc->col[j];
-            c.bb = t; c.rr[0] = t; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
-            c.stop = j < nrhs ? 0 : 1;
+            c.bb = t; c.rr[0] = rr0; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
+            c.stop = born_stopped ? 1 : 0;
             if constexpr (PC) { sc->rz[j][0] = tz; sc->rz[j][1] = 0.0; }
         }
     }
     if (threadIdx.x == 0) {
-        sc->all_stop = 0;
         sc->pad = 0;
-        post_progress(host_flags, 0, false);
+        if constexpr (GUESS) {
+            sc->all_stop = all ? 1 : 0;
+            post_progress_word(host_flags, 0, all ? 1 : 0);
+        } else {
+            sc->all_stop = 0;
+            post_progress(host_flags, 0, false);
+        }
+    }
+}
+
+// lam_hip_true_residual_many: with AX = A X from one batched product, per column r = b - A x rounded to the vector dtype;
+// per-workgroup fp64 partials of r_j.r_j and of b_j.b_j, both at [j * gridDim.x + block]
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+multi_residual_kernel(const TV *__restrict__ B, const TV *__restrict__ AX, uint64_t n, double *__restrict__ partial_rr,
+                      double *__restrict__ partial_bb)
+{
+    __shared__ double s_red[kWaves];
+    double acc[K], accb[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = accb[j] = 0.0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const TV bi = B[i * K + j];
+            const TV ri = bi - AX[i * K + j];
+            acc[j] += (double)ri * (double)ri;
+            accb[j] += (double)bi * (double)bi;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        const double tb = block_sum(accb[j], s_red);
+        if (threadIdx.x == 0) {
+            partial_rr[(size_t)j * gridDim.x + blockIdx.x] = t;
+            partial_bb[(size_t)j * gridDim.x + blockIdx.x] = tb;
+        }
+    }
+}
+// out[j] = sqrt(r_j.r_j / b_j.b_j) for the K columns of the instantiation (plain IEEE: b_j = 0 gives 0/0); one workgroup
+template <int K>
+__global__ void __launch_bounds__(kBlock)
+multi_residual_scalars_kernel(const double *__restrict__ red_rr, const double *__restrict__ red_bb, int nred, double *__restrict__ out)
+{
+    __shared__ double s_red[kWaves];
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum_array(red_rr + (size_t)j * nred, nred, s_red);
+        const double tb = block_sum_array(red_bb + (size_t)j * nred, nred, s_red);
+        if (threadIdx.x == 0) out[j] = sqrt(t / tb);
     }
 }
 

@@ -1,5 +1,5 @@
-// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _solve_many / _solve_many_pc / _get_solution_many /
-// _gemv_many / _gemv_many_only, and lam_hip_get_diagonal.  nrhs independent CG recurrences (NOT block CG) advanced together, one
+// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _solve_many / _solve_many_pc / _solve_many_x0 /
+// _true_residual_many / _get_solution_many / _gemv_many / _gemv_many_only, and lam_hip_get_diagonal.  nrhs independent CG recurrences (NOT block CG) advanced together, one
 // pass over the matrix per iteration.
 // Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 //
@@ -9,7 +9,8 @@
 // Three launches per iteration (product; x, r; p), all on shard 0's stream; the host follows the batch's own pinned progress word
 // with the lag rule of the single solve (lag_check), where "stopped" means every live column has stopped.
 // One recurrence in the source: lam_hip_solve_many_pc(JACOBI) runs the PC = true instantiations of the same four vector kernels
-// (multi_init_kernel, multi_init_scalars_kernel, multi_xr_kernel, multi_p_kernel) on the same scalars' block.
+// (multi_init_kernel, multi_init_scalars_kernel, multi_xr_kernel, multi_p_kernel) on the same scalars' block, and
+// lam_hip_solve_many_x0 the GUESS = true instantiations of the two init kernels behind one more product launch; the loop is shared.
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
@@ -32,7 +33,7 @@ void multi_release(lam_hip_ctx *c)
     if (c->sh[0].stream) (void)hipStreamSynchronize(c->sh[0].stream);
     free_dev({c->pcg.diag, c->pcg.dinv, c->pcg.part_rz, c->pcg.info});
     c->pcg = PcgState();
-    free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.sc});
+    free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.part_rr, m.res, m.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -73,6 +74,8 @@ int multi_ensure(lam_hip_ctx *c)
     for (auto v : vecs) HIPCHK(c, hipMalloc(v, elems * ev));
     HIPCHK(c, hipMalloc((void **)&m.part_gemv, sizeof(double) * kMaxRhs * (size_t)c->n));
     HIPCHK(c, hipMalloc((void **)&m.part_vec, sizeof(double) * kMaxRhs * kVecBlocksMax));
+    HIPCHK(c, hipMalloc((void **)&m.part_rr, sizeof(double) * kMaxRhs * kVecBlocksMax));
+    HIPCHK(c, hipMalloc((void **)&m.res, sizeof(double) * kMaxRhs));
     HIPCHK(c, hipMalloc((void **)&m.sc, sizeof(BatchScalars)));
     HIPCHK(c, hipHostMalloc((void **)&m.sc_host, sizeof(MultiScalars), hipHostMallocDefault));
     HIPCHK(c, hipHostMalloc((void **)&m.host_flags, 64, hipHostMallocDefault));
@@ -114,6 +117,15 @@ template <typename F>
 int multi_dispatch(lam_hip_ctx *c, int K, bool pc, F &&f)
 {
     return multi_dispatch(c, K, [&](auto impl, auto k) -> int { return pc ? f(impl, k, std::true_type()) : f(impl, k, std::false_type()); });
+}
+
+// and with the start: f(..., bool_constant<PC>(), bool_constant<GUESS>()), GUESS = from an initial guess (lam_hip_solve_many_x0)
+template <typename F>
+int multi_dispatch(lam_hip_ctx *c, int K, bool pc, bool guess, F &&f)
+{
+    return multi_dispatch(c, K, pc, [&](auto impl, auto k, auto pct) -> int {
+        return guess ? f(impl, k, pct, std::true_type()) : f(impl, k, pct, std::false_type());
+    });
 }
 
 int multi_gemv_grid(const lam_hip_ctx *c) { return (int)((c->n + kMultiRows - 1) / kMultiRows); }
@@ -160,6 +172,17 @@ int multi_download(lam_hip_ctx *c, int nrhs, int K, const void *src, void *host)
     }));
     HIPCHK(c, hipMemcpyAsync(host, m.stage, (size_t)nrhs * c->n * c->esz_v(), hipMemcpyDeviceToHost, s.stream));
     HIPCHK(c, hipStreamSynchronize(s.stream));
+    return 0;
+}
+
+// P = X of the batch's last solve, ready for the product: the rows behind row n zero in this K's layout (X's are not kept so)
+int multi_stage_solution(lam_hip_ctx *c, int K)
+{
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    const size_t ev = c->esz_v(), body = (size_t)c->n * K * ev;
+    HIPCHK(c, hipMemcpyAsync(m.P, m.X, body, hipMemcpyDeviceToDevice, s.stream));
+    HIPCHK(c, hipMemsetAsync((char *)m.P + body, 0, (size_t)kMultiPadRows * K * ev, s.stream));
     return 0;
 }
 
@@ -251,12 +274,17 @@ int lam_hip_set_rhs_many(lam_hip_ctx *c, int nrhs, const void *b_host)
 
 namespace {
 
-// lam_hip_solve_many (precond = LAM_HIP_PC_NONE) and lam_hip_solve_many_pc: one body, one sequence of launches.  The
-// Jacobi-preconditioned batch runs the PC = true instantiations of the four vector kernels on dinv and a second partial array (both
-// null for the plain batch); the product launch, the scalars' block, the progress word, the lag rule and the per-column results are
-// shared.
-int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters,
-                int32_t *converged, double *rel_err)
+// where a batched solve starts: x = 0, a guess given on the host, or the batch's own last solution
+enum MultiGuess { kGuessNone, kGuessHost, kGuessCurrent };
+
+// lam_hip_solve_many (precond = LAM_HIP_PC_NONE), lam_hip_solve_many_pc and lam_hip_solve_many_x0: one body, one sequence of
+// launches.  The Jacobi-preconditioned batch runs the PC = true instantiations of the four vector kernels on dinv and a second
+// partial array (both null for the plain batch); the product launch, the scalars' block, the progress word, the lag rule and the
+// per-column results are shared.  A start from a guess stages the guess in P (whose rows behind row n the product needs zero; the
+// upload and multi_stage_solution see to that), forms A x0 in AP with one more product launch and runs the GUESS = true
+// instantiations of the two init kernels; the loop is the same loop.
+int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, const void *x0_host, int max_iters, double rel_error,
+                lam_hip_stats *st, int32_t *num_iters, int32_t *converged, double *rel_err)
 {
     LAMCHK(multi_supported(c, fn));
     if (precond != LAM_HIP_PC_NONE && precond != LAM_HIP_PC_JACOBI)
@@ -266,6 +294,8 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, doub
     MultiState &m = c->multi;
     if (!c->have_matrix || !m.have_rhs || m.n != c->n)
         return fail(c, LAM_HIP_ESTATE, "matrix and right-hand sides (lam_hip_set_rhs_many) must be set before %s", fn);
+    if (guess == kGuessCurrent && !m.solved)
+        return fail(c, LAM_HIP_ESTATE, "%s: x0_host is NULL and there is no batched solution to continue from (lam_hip_solve_many)", fn);
     const double t0 = now_s();
     ShardBase &s0 = c->sh[0];
     LAMCHK(set_dev(c, s0));
@@ -289,20 +319,27 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, int max_iters, doub
     const int vb = vec_grid(c->n), gb = multi_gemv_grid(c);
     double gemv_ms = 0.0;
     int samples = 0, enq = 0;
-    LAMCHK(multi_dispatch(c, m.K, pc, [&](auto impl, auto kc, auto pct) -> int {
+    if (guess == kGuessHost) LAMCHK(multi_upload(c, m.nrhs, m.K, x0_host, m.P));
+    if (guess == kGuessCurrent) LAMCHK(multi_stage_solution(c, m.K));
+    LAMCHK(multi_dispatch(c, m.K, pc, guess != kGuessNone, [&](auto impl, auto kc, auto pct, auto gt) -> int {
         using I = decltype(impl);
         using TA = typename ImplTraits<I>::TA;
         using TV = typename ImplTraits<I>::TV;
         constexpr int K = decltype(kc)::value;
         constexpr bool PC = decltype(pct)::value;
+        constexpr bool GUESS = decltype(gt)::value;
         const TV *const dinv = PC ? (const TV *)g.dinv : nullptr;
         double *const part_rz = PC ? g.part_rz : nullptr;
-        // x = 0, r = b, p = b, bb_j = b_j.b_j  (PC: p = dinv o b, rz_j = b_j.(dinv o b_j))
-        hipLaunchKernelGGL((multi_init_kernel<TV, K, PC>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X, (TV *)m.R,
-                           (TV *)m.P, c->n, m.part_vec, dinv, part_rz);
+        double *const part_rr = GUESS ? m.part_rr : nullptr;
+        // GUESS: AP = A x0 of the guess staged in P, outside the iteration's scalars and partials
+        if (GUESS) LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr)));
+        // x = 0, r = b, p = b, bb_j = b_j.b_j  (PC: p = dinv o b, rz_j = b_j.(dinv o b_j));  GUESS: x = x0, r = b - A x0, p = r,
+        // rr_j = r_j.r_j next to bb_j  (PC: p = dinv o r, rz_j = r_j.(dinv o r_j))
+        hipLaunchKernelGGL((multi_init_kernel<TV, K, PC, GUESS>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X,
+                           (TV *)m.R, (TV *)m.P, c->n, m.part_vec, dinv, part_rz, (const TV *)(GUESS ? m.AP : nullptr), part_rr);
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL((multi_init_scalars_kernel<K, PC>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs,
-                           m.sc, (volatile int *)m.host_flags, (const double *)part_rz);
+        hipLaunchKernelGGL((multi_init_scalars_kernel<K, PC, GUESS>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb,
+                           m.nrhs, m.sc, (volatile int *)m.host_flags, (const double *)part_rz, (const double *)part_rr, rel_error);
         HIPCHK(c, hipGetLastError());
         for (int i = 0; i < max_iters; i++) {
             const int k = i + 1, slot = i % kLag;
@@ -377,14 +414,58 @@ int lam_hip_solve_many(lam_hip_ctx *c, int max_iters, double rel_error, lam_hip_
                        double *rel_err)
 {
     if (!c) return LAM_HIP_EINVAL;
-    return multi_solve(c, "lam_hip_solve_many", LAM_HIP_PC_NONE, max_iters, rel_error, st, num_iters, converged, rel_err);
+    return multi_solve(c, "lam_hip_solve_many", LAM_HIP_PC_NONE, kGuessNone, nullptr, max_iters, rel_error, st, num_iters, converged, rel_err);
 }
 
 int lam_hip_solve_many_pc(lam_hip_ctx *c, int precond, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters,
                           int32_t *converged, double *rel_err)
 {
     if (!c) return LAM_HIP_EINVAL;
-    return multi_solve(c, "lam_hip_solve_many_pc", precond, max_iters, rel_error, st, num_iters, converged, rel_err);
+    return multi_solve(c, "lam_hip_solve_many_pc", precond, kGuessNone, nullptr, max_iters, rel_error, st, num_iters, converged, rel_err);
+}
+
+int lam_hip_solve_many_x0(lam_hip_ctx *c, int precond, const void *x0_host, int max_iters, double rel_error, lam_hip_stats *st,
+                          int32_t *num_iters, int32_t *converged, double *rel_err)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    return multi_solve(c, "lam_hip_solve_many_x0", precond, x0_host ? kGuessHost : kGuessCurrent, x0_host, max_iters, rel_error, st,
+                       num_iters, converged, rel_err);
+}
+
+// One batched product of X (staged through P, whose rows behind row n the product needs zero), one K-wide pass over B and A X, one
+// workgroup for the K quotients.  B, X and the scalars are left alone; P and AP are scratch, as they are between any two solves.
+int lam_hip_true_residual_many(lam_hip_ctx *c, int nrhs, double *rel_res)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_true_residual_many"));
+    LAMCHK(multi_check_nrhs(c, "lam_hip_true_residual_many", nrhs));
+    if (!rel_res) return fail(c, LAM_HIP_EINVAL, "lam_hip_true_residual_many: rel_res is NULL");
+    MultiState &m = c->multi;
+    if (!m.solved || !m.have_rhs || m.n != c->n) return fail(c, LAM_HIP_ESTATE, "no batched solution yet (lam_hip_solve_many)");
+    if (nrhs > m.nrhs) return fail(c, LAM_HIP_EINVAL, "lam_hip_true_residual_many: %d columns asked, %d were solved", nrhs, m.nrhs);
+    ShardBase &s = c->sh[0];
+    LAMCHK(set_dev(c, s));
+    LAMCHK(multi_stage_solution(c, m.K));
+    const int vb = vec_grid(c->n);
+    LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc) -> int {
+        using I = decltype(impl);
+        using TA = typename ImplTraits<I>::TA;
+        using TV = typename ImplTraits<I>::TV;
+        constexpr int K = decltype(kc)::value;
+        LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr)));
+        hipLaunchKernelGGL((multi_residual_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s.stream, (const TV *)m.B, (const TV *)m.AP, c->n,
+                           m.part_rr, m.part_vec);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((multi_residual_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s.stream, (const double *)m.part_rr,
+                           (const double *)m.part_vec, vb, m.res);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }));
+    double res[kMaxRhs];
+    HIPCHK(c, hipMemcpyAsync(res, m.res, sizeof(double) * m.K, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    for (int j = 0; j < nrhs; j++) rel_res[j] = res[j];
+    return 0;
 }
 
 // Single-process contexts, any number of shards, every storage type: each shard's device extracts its own rows' diagonal elements.

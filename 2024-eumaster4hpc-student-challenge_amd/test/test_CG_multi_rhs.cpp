@@ -1,8 +1,12 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
-//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
+// -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
+// for the remaining max_iters - W; num_iters is the two stages' sum, rel_err the second stage's.
+// -T: each column's true residual ||b - A x|| / ||b|| (lam_hip_true_residual_many) as one more CSV column behind t_cg.
+// Without the two flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
 //     rows,procs,threads,t_load,t_comm_init,t_gemv,t_iter,num_iters,rel_err,t_cg
@@ -19,7 +23,7 @@
 #include "LAM.hpp"
 
 template <typename T>
-static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi)
+static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi, int warm, bool true_res)
 {
     using clk = std::chrono::high_resolution_clock;
     LAM::ConjugateGradient_HIP<T> cg(0);
@@ -36,14 +40,34 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
     std::vector<int32_t> iters(nrhs), conv(nrhs);
     std::vector<double> rel(nrhs);
     const auto t1 = clk::now();
-    if (jacobi) cg.solve_many_pc(LAM_HIP_PC_JACOBI, nrhs, B.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data());
-    else cg.solve_many(nrhs, B.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data());
+    const int pc = jacobi ? LAM_HIP_PC_JACOBI : LAM_HIP_PC_NONE;
+    if (warm >= 0) {
+        // stage 1 from a zero guess (the plain solve, bit for bit), stage 2 from its solution; 0 iterations is an answer here,
+        // so failure is the call's own report
+        const std::vector<T> zero((size_t)nrhs * rows, (T)0);
+        std::vector<int32_t> first(nrhs);
+        cg.solve_many_x0(pc, nrhs, B.data(), zero.data(), nullptr, warm, (T)rel_error, first.data(), conv.data(), rel.data());
+        if (cg.batch_failed()) return 3;
+        // a column that stopped in stage 1 is born stopped in stage 2 (0 more iterations); one that hit the cap reports W + 1
+        for (int j = 0; j < nrhs; j++) first[j] = conv[j] ? first[j] : warm;
+        cg.solve_many_x0(pc, nrhs, nullptr, nullptr, nullptr, max_iters - warm, (T)rel_error, iters.data(), conv.data(), rel.data());
+        if (cg.batch_failed()) return 3;
+        for (int j = 0; j < nrhs; j++) iters[j] += first[j];
+    } else {
+        if (jacobi) cg.solve_many_pc(pc, nrhs, B.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data());
+        else cg.solve_many(nrhs, B.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data());
+        if (cg.batch_failed()) return 3;               // the solve itself failed (reported on stderr)
+    }
     const double t_cg = std::chrono::duration<double>(clk::now() - t1).count();
-    if (cg.stats().num_iters == 0) return 3;       // the solve itself failed (reported on stderr)
+    std::vector<double> tres(nrhs);
+    if (true_res && !cg.true_residual_many(nrhs, tres.data())) return 3;
     const lam_hip_stats &st = cg.stats();
-    for (int j = 0; j < nrhs; j++)
+    for (int j = 0; j < nrhs; j++) {
         std::cout << rows << "," << 1 << "," << 1 << "," << t_load << "," << st.t_comm_init << "," << st.t_gemv << "," << st.t_iter << ","
-                  << iters[j] << "," << rel[j] << "," << t_cg << std::endl;
+                  << iters[j] << "," << rel[j] << "," << t_cg;
+        if (true_res) std::cout << "," << tres[j];
+        std::cout << std::endl;
+    }
     return 0;
 }
 
@@ -53,8 +77,10 @@ int main(int argc, char **argv)
     int nrhs = 1, max_iters = 1000, opt;
     double rel_error = 1e-9;
     const char *precision = "f64";
-    bool jacobi = false;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jh")) != -1) {
+    bool jacobi = false, true_res = false;
+    int warm = -1;                  // -1: no -w
+    bool bad_warm = false;
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:Th")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); break;
@@ -62,18 +88,21 @@ int main(int argc, char **argv)
         case 'e': rel_error = atof(optarg); break;
         case 't': precision = optarg; break;
         case 'J': jacobi = true; break;
+        case 'w': warm = atoi(optarg); bad_warm = warm < 0; break;
+        case 'T': true_res = true; break;
         default:
-            fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)]\n", argv[0]);
+            fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
+                    "[-T (true residuals)]\n", argv[0]);
             return opt == 'h' ? 0 : 1;
         }
     }
-    if (rows == 0 || nrhs < 1 || nrhs > LAM_HIP_MAX_RHS || max_iters < 0) {
-        fprintf(stderr, "Usage: %s -s N -k nrhs (1..%d) -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)]\n", argv[0],
-                LAM_HIP_MAX_RHS);
+    if (rows == 0 || nrhs < 1 || nrhs > LAM_HIP_MAX_RHS || max_iters < 0 || bad_warm || warm > max_iters) {
+        fprintf(stderr, "Usage: %s -s N -k nrhs (1..%d) -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (0..max_iters)] [-T]\n",
+                argv[0], LAM_HIP_MAX_RHS);
         return 1;
     }
-    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi);
-    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi);
+    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res);
+    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res);
     fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
     return 1;
 }

@@ -48,7 +48,8 @@ extern "C" {
  *      lam_hip_solve_many, lam_hip_get_solution_many, lam_hip_gemv_many, lam_hip_gemv_many_only and the get-only option
  *      "multi_rhs_k".  A caller that needs them checks for the symbols (dlsym) or the build id; the version number does not move.
  *      Added under version 4 likewise (purely additive): LAM_HIP_PC_NONE, LAM_HIP_PC_JACOBI, lam_hip_solve_many_pc and
- *      lam_hip_get_diagonal. */
+ *      lam_hip_get_diagonal.
+ *      Added under version 4 likewise (purely additive): lam_hip_solve_many_x0 and lam_hip_true_residual_many. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -264,6 +265,36 @@ int lam_hip_solve_many(lam_hip_ctx *ctx, int max_iters, double rel_error, lam_hi
 #define LAM_HIP_PC_JACOBI 1
 int lam_hip_solve_many_pc(lam_hip_ctx *ctx, int precond, int max_iters, double rel_error, lam_hip_stats *stats,
                           int32_t *num_iters, int32_t *converged, double *rel_err);
+/* lam_hip_solve_many_pc(precond, ...) started from an initial guess instead of from x = 0.  x0_host: the nrhs guesses of the last
+ * lam_hip_set_rhs_many, laid out as B (vector j at x0_host + j*N, vector dtype).  x0_host == NULL: from the batch's current
+ * solution X -- the restart (fresh r = b - A x in place of a recursive residual that has drifted) or the continuation (a run that
+ * hit its cap) of the last lam_hip_solve_many* call on this context; LAM_HIP_ESTATE if there is no readable batched solution:
+ * before the first solve, after a refused diagonal, after lam_hip_gemv_many / _many_only, after a new matrix or
+ * lam_hip_set_problem.  Per column j, independently:
+ *     x = x0, r = b - A x0 (rounded to the vector dtype), bb = b.b, rr = r.r, p = r         (Jacobi: p = dinv o r, rz = r.(dinv o r))
+ *     k = 0: if sqrt(rr/bb) < rel_error the column is born stopped: num_iters = 0, converged = 1, x = x0 bit for bit
+ *     k = 1..max_iters: the loop of lam_hip_solve_many_pc, unchanged
+ * One more product launch (A x0) and a fused K-wide pass in front of the loop; t_total includes them, gemv_bytes is the loop's
+ * product launch as before.  bb = b.b stays the stop test's denominator, so rel_error keeps meaning "relative to ||b||" and a
+ * continuation stops where the uninterrupted run would be asked to stop.
+ *   - the k = 0 test is what keeps an exact guess (r = 0) from alpha = 0/0.  With rel_error <= 0 nothing ever stops, as in every
+ *     solve here, k = 0 included: an exact guess then runs on 0/0 to the cap and its column ends as NaN, like a b_j = 0 column;
+ *   - IDENTITY: for a finite matrix and rel_error <= 1, an all-zero x0_host gives the x, the per-column num_iters / converged /
+ *     rel_err and "multi_rhs_k" of lam_hip_solve_many_pc(precond, ...) bit for bit (r = b - 0 = b exactly, and r.r and r.z are
+ *     summed in the order that call sums b.b and b.(dinv o b)).  With rel_error > 1 the zero guess itself meets the test at k = 0;
+ *   - max_iters = 0 is legal and returns the k = 0 state: rel_err = sqrt(rr0/bb), num_iters = 0 for a born-stopped column and
+ *     max_iters + 1 = 1 otherwise;
+ *   - everything else is lam_hip_solve_many_pc's: what is supported and what is refused (same codes), an unknown `precond`, the
+ *     frozen state of a stopped column, the confinement of NaN / Inf to their column (a NaN in column j of x0 included),
+ *     max_iters + 1 at the cap, the Jacobi diagonal's refusal (after which there is no batched solution). */
+int lam_hip_solve_many_x0(lam_hip_ctx *ctx, int precond, const void *x0_host, int max_iters, double rel_error,
+                          lam_hip_stats *stats, int32_t *num_iters, int32_t *converged, double *rel_err);
+/* rel_res[j] = ||b_j - A x_j||_2 / ||b_j||_2 for the first nrhs columns of the last batched solution: ONE batched product of X,
+ * then one K-wide pass (b - A x rounded to the vector dtype, fp64 sums).  The counterpart of lam_hip_true_residual, which serves
+ * the single solve only.  The quotient is plain IEEE: b_j = 0 gives 0/0.  nrhs beyond the number solved: LAM_HIP_EINVAL; no
+ * batched solution: LAM_HIP_ESTATE.  B and X are left alone: the solution stays readable and a following
+ * lam_hip_solve_many_x0(..., NULL, ...) continues from it.  Independent of the single-vector state, as all batch calls are. */
+int lam_hip_true_residual_many(lam_hip_ctx *ctx, int nrhs, double *rel_res);
 /* The stored diagonal A[i][i], N elements of the vector dtype (LAM_HIP_BF16 storage: the stored bf16 values as float, exactly),
  * extracted on the device(s) from the pitched matrix.  Single-process contexts with any number of shards, every storage type;
  * rank mode: LAM_HIP_EINVAL; no matrix set: LAM_HIP_ESTATE.  No reference counterpart: the reference is un-preconditioned
