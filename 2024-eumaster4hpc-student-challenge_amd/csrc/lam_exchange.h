@@ -804,6 +804,51 @@ int enqueue_iteration_direct(lam_hip_ctx *c, int k, double rel_error, int slot)
     });
 }
 
+// gather-Ap exchange, the end of cg_init on every topology: each local shard holds b in r_full; p = r = b, x = 0, b.b
+template <typename TV>
+int finish_cg_init_exchange1(lam_hip_ctx *c)
+{
+    const int grid = vec_grid(c->n);
+    for (auto &s : c->sh) {
+        if (!c->rank_mode) LAMCHK(set_dev(c, s));       // rank mode: the one local shard's device is current already
+        hipLaunchKernelGGL((cg_init_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (TV *)s.r_full, (TV *)s.p,
+                           (TV *)s.x, c->n, s.nrows, s.part_vec);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_vec, grid, s.sc);
+        HIPCHK(c, hipGetLastError());
+    }
+    LAMCHK(arm_partials(c));
+    c->k_done = 0;
+    c->cg_ready = true;
+    c->cg_exchange1 = true;
+    return 0;
+}
+
+// gather-Ap exchange, the full-length vector step of one shard once `nrec` records are in `gathered`: alpha, its x slice, FULL r and
+// p, the stop test -- in ONE launch (r.r resolved by its reducer workgroup: 2 launches per shard and iteration) or as two kernels
+template <typename TV>
+int launch_full_vector_step(lam_hip_ctx *c, ShardBase &s, const char *gathered, uint64_t stride, uint64_t base, int nrec, int k,
+                            double rel_error, bool sym)
+{
+    const int grid = vec_grid(c->n);
+    if (c->fuse_active) {
+        const unsigned long long seq = c->seq_base + (unsigned)k;      // the tag of the launch's hand-over, see seq_base
+        c->seq_span = std::max<uint64_t>(c->seq_span, (uint64_t)k + 1);
+        hipLaunchKernelGGL((update_full_fused_kernel<TV>), dim3(grid + 1), dim3(kBlock), 0, s.stream, gathered, stride,
+                           base, nrec, s.sc, k, rel_error, (TV *)s.p, (TV *)s.x, (TV *)s.r_full, c->n, s.row0, s.nrows, s.part_vec,
+                           grid, s.bcast, seq, c->direct_err, (volatile int *)s.host_flags, sym ? 1 : 0);
+        LAUNCHED(c);
+        return 0;
+    }
+    hipLaunchKernelGGL((update_xr_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, gathered, stride,
+                       base, nrec, s.sc, k, (const TV *)s.p, (TV *)s.x, (TV *)s.r_full, c->n, s.row0, s.nrows, s.part_vec, sym ? 1 : 0);
+    LAUNCHED(c);
+    hipLaunchKernelGGL((update_p_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (const double *)s.part_vec, grid, s.sc,
+                       k, rel_error, (const TV *)s.r_full, (TV *)s.p, c->n, (volatile int *)s.host_flags);
+    LAUNCHED(c);
+    return 0;
+}
+
 // gather-Ap exchange, one process with several shards: CG state = x slice, FULL r and p on every shard.  The rhs
 // slices are replicated once with peer copies (the rank mode's one-off all-gather), after that no vector is exchanged
 // but Ap.
@@ -818,20 +863,7 @@ int do_cg_init_exchange1_local(lam_hip_ctx *c)
             for (auto &src : c->sh)
                 HIPCHK(c, hipMemcpyAsync((char *)dst.r_full + src.row0 * ev, src.b, src.nrows * ev, hipMemcpyDefault, dst.stream));
         }
-        const int grid = vec_grid(c->n);
-        for (auto &s : c->sh) {
-            LAMCHK(set_dev(c, s));
-            hipLaunchKernelGGL((cg_init_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (TV *)s.r_full, (TV *)s.p,
-                               (TV *)s.x, c->n, s.nrows, s.part_vec);
-            HIPCHK(c, hipGetLastError());
-            hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_vec, grid, s.sc);
-            HIPCHK(c, hipGetLastError());
-        }
-        LAMCHK(arm_partials(c));
-        c->k_done = 0;
-        c->cg_ready = true;
-        c->cg_exchange1 = true;
-        return 0;
+        return finish_cg_init_exchange1<TV>(c);
     });
 }
 
@@ -934,9 +966,6 @@ int enqueue_iteration_exchange1_local(lam_hip_ctx *c, int k, double rel_error, i
             LAMCHK(xt_end(c, s0, s0.stream));
             RECORD(c, c->ev_join[0], s0.stream);
         }
-        const int grid = vec_grid(c->n);
-        const unsigned long long seq = c->seq_base + (unsigned)k;
-        c->seq_span = std::max<uint64_t>(c->seq_span, (uint64_t)k + 1);
         for (auto &s : c->sh) {
             LAMCHK(set_dev(c, s));
             if (c->opt_join) {
@@ -946,20 +975,7 @@ int enqueue_iteration_exchange1_local(lam_hip_ctx *c, int k, double rel_error, i
                     if (&t != &s) WAITEV(c, s.stream, t.ev_a);
                 LAMCHK(xt_end(c, s, s.stream));
             }
-            if (c->fuse_active) {
-                // the two vector kernels in ONE launch (r.r resolved by its reducer workgroup): 2 launches per shard and iteration
-                hipLaunchKernelGGL((update_full_fused_kernel<TV>), dim3(grid + 1), dim3(kBlock), 0, s.stream, (const char *)buf(s), stride,
-                                   base, P, s.sc, k, rel_error, (TV *)s.p, (TV *)s.x, (TV *)s.r_full, c->n, s.row0, s.nrows, s.part_vec,
-                                   grid, s.bcast, seq, c->direct_err, (volatile int *)s.host_flags, sym ? 1 : 0);
-                LAUNCHED(c);
-                continue;
-            }
-            hipLaunchKernelGGL((update_xr_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (const char *)buf(s), stride,
-                               base, P, s.sc, k, (const TV *)s.p, (TV *)s.x, (TV *)s.r_full, c->n, s.row0, s.nrows, s.part_vec, sym ? 1 : 0);
-            LAUNCHED(c);
-            hipLaunchKernelGGL((update_p_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (const double *)s.part_vec, grid, s.sc,
-                               k, rel_error, (const TV *)s.r_full, (TV *)s.p, c->n, (volatile int *)s.host_flags);
-            LAUNCHED(c);
+            LAMCHK(launch_full_vector_step<TV>(c, s, buf(s), stride, base, P, k, rel_error, sym));
         }
         return 0;
     });
@@ -992,17 +1008,7 @@ int do_cg_init_exchange1(lam_hip_ctx *c)
             }
             NCCLCHK(c, ncclGroupEnd());
         }
-        const int grid = vec_grid(c->n);
-        hipLaunchKernelGGL((cg_init_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (TV *)s.r_full, (TV *)s.p,
-                           (TV *)s.x, c->n, s.nrows, s.part_vec);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(cg_init_scalars_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_vec, grid, s.sc);
-        HIPCHK(c, hipGetLastError());
-        LAMCHK(arm_partials(c));
-        c->k_done = 0;
-        c->cg_ready = true;
-        c->cg_exchange1 = true;
-        return 0;
+        return finish_cg_init_exchange1<TV>(c);
     });
 }
 
@@ -1058,26 +1064,8 @@ int enqueue_iteration_exchange1(lam_hip_ctx *c, int k, double rel_error, int slo
         NCCLCHK(c, ncclAllGather(rec, gathered, stride, ncclChar, c->comm, s.stream));
         c->n_collectives++;
         LAMCHK(xt_end(c, s, s.stream));
-        // 3. alpha, x slice, FULL r (+ partials of r.r over the full vector: no collective needed)
-        const int grid = vec_grid(c->n);
-        if (c->fuse_active) {
-            // 3 + 4 in ONE launch: GEMV, collective, vector step
-            const unsigned long long seq = c->seq_base + (unsigned)k;
-            c->seq_span = std::max<uint64_t>(c->seq_span, (uint64_t)k + 1);
-            hipLaunchKernelGGL((update_full_fused_kernel<TV>), dim3(grid + 1), dim3(kBlock), 0, s.stream, (const char *)gathered, stride,
-                               base, c->nranks, s.sc, k, rel_error, (TV *)s.p, (TV *)s.x, (TV *)s.r_full, c->n, s.row0, s.nrows, s.part_vec,
-                               grid, s.bcast, seq, c->direct_err, (volatile int *)s.host_flags, sym ? 1 : 0);
-            LAUNCHED(c);
-            return 0;
-        }
-        hipLaunchKernelGGL((update_xr_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (const char *)gathered, stride,
-                           base, c->nranks, s.sc, k, (const TV *)s.p, (TV *)s.x, (TV *)s.r_full, c->n, s.row0, s.nrows, s.part_vec, sym ? 1 : 0);
-        LAUNCHED(c);
-        // 4. beta, stop test, FULL p
-        hipLaunchKernelGGL((update_p_full_kernel<TV>), dim3(grid), dim3(kBlock), 0, s.stream, (const double *)s.part_vec, grid, s.sc,
-                           k, rel_error, (const TV *)s.r_full, (TV *)s.p, c->n, (volatile int *)s.host_flags);
-        LAUNCHED(c);
-        return 0;
+        // 3. alpha, x slice, FULL r (+ partials of r.r over the full vector: no collective needed); 4. beta, stop test, FULL p
+        return launch_full_vector_step<TV>(c, s, gathered, stride, base, c->nranks, k, rel_error, sym);
     });
 }
 

@@ -2,7 +2,7 @@
 //
 // Reference counterparts (semantics only; nothing here is derived from that code):
 //   gemv / partialDot / reduce / dot / divide / axpy / minusaxpy / xpby CUDA kernels,
-//   /root/reference/challenge/main/LAM/src/GPU/distributed/ConjugateGradient_MultiGPUS_CUDA_NCCL.cu:34-238
+//   challenge/main/LAM/src/GPU/distributed/ConjugateGradient_MultiGPUS_CUDA_NCCL.cu:34-238 of the reference
 //   and the CPU members dot/axpby/gemv, LAM/src/CPU/ConjugateGradient_CPU_MPI_OMP.hpp:446-508.
 //
 // Design:
@@ -14,6 +14,11 @@
 //                          every shard's replicated p)
 //     alpha, beta, rr, the stop flag and the iteration counter live in device memory
 //     (CgScalars); the host never has to read a scalar to enqueue the next iteration.
+//   * the vector step's recurrence -- alpha, the x / r sweep, the gathered p.Ap, beta and the stop test, the p sweep -- is written
+//     ONCE, as the device helpers cg_alpha, sweep_xr, gathered_pap, cg_decide, sweep_p and sweep_p_slice at the head of the
+//     section "vector kernels".  Its six kernels (two kernels or one launch, on sliced or on full-length vectors) only say which
+//     workgroup reduces, computes or waits, where p.Ap and r.r come from and which elements a thread sweeps; the tuning build's
+//     cg_persist_kernel shares cg_decide.  That the forms agree bit for bit holds by construction.
 //   * all reductions are two-stage and fixed-order (no floating-point atomics): results are
 //     bit-reproducible run to run and identical on every shard.
 //   * GEMV is HBM-bound (0.25 flop/B in fp64).  Production shape (gemv_coop_kernel): the 4 waves of a
@@ -54,7 +59,7 @@ struct CgScalars {
     double alpha;
     double beta;
     int iters;        // last completed iteration (the converging one once stop is set)
-    int stop;         // set by update_p_kernel when sqrt(rr/bb) < rel_error
+    int stop;         // set by cg_decide (the vector step) when sqrt(rr/bb) < rel_error
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1530,6 +1535,13 @@ gemv_generic_kernel(GemvArgs<TA, TV> a)
 
 // ---------------------------------------------------------------------------------------------
 // vector kernels
+//   cg_init: finalize_sum_kernel, cg_init_kernel, cg_init_scalars_kernel (cg_init_full_kernel with the gather-Ap exchange below);
+//   the vector step alpha = rr / p.Ap; x += alpha p; r -= alpha Ap; r.r; beta; the stop test; p = r + beta p:
+//                         sliced vectors (one shard, exchange 0 and 2)   full-length vectors (gather-Ap exchange)
+//       two kernels       update_xr_kernel, update_p_kernel              update_xr_full_kernel, update_p_full_kernel
+//       one launch        update_fused_kernel                            update_full_fused_kernel
+//   every statement of it is in the helpers in front of update_xr_kernel (and gathered_ap / gathered_pap in front of
+//   update_xr_full_kernel); a kernel body is its role split plus calls to them.
 // ---------------------------------------------------------------------------------------------
 // sum src[0..n) with one workgroup and store it at index `slot` of every destination array
 // (cg_init only: inside the iteration the producer kernels do this themselves, see Finalize)
@@ -1580,8 +1592,102 @@ cg_init_scalars_kernel(const double *__restrict__ red, int nred, CgScalars *sc)
     }
 }
 
-// alpha = rr / p.Ap ; x += alpha p ; r -= alpha Ap ; partials of r.r
+// ---- The recurrence of the vector step, written ONCE.  The six kernels below (update_xr / update_p / update_fused on sliced
+// vectors, update_xr_full / update_p_full / update_full_fused on full-length ones) are a role split -- who reduces, who computes,
+// who waits, where p.Ap and r.r come from -- around these helpers, so "fused vs two kernels", "one process vs rank mode" and
+// "exchange 2 vs 0" run the same statements by construction.  A caller supplies the first index and the stride of its sweeps
+// (its element -> thread mapping) and says which thread is the leader that keeps CgScalars.
+
+// alpha = rr / p.Ap, in double and in the vectors' type; rr = r.r of the previous iteration
+template <typename TV> struct CgAlpha { double rr, alpha_d; TV alpha; };
+template <typename TV>
+__device__ __forceinline__ CgAlpha<TV> cg_alpha(const CgScalars *sc, int k, double pAp)
+{
+    CgAlpha<TV> a;
+    a.rr = sc->rr[(k + 1) & 1];
+    a.alpha_d = a.rr / pAp;
+    a.alpha = (TV)a.alpha_d;
+    return a;
+}
+
+// r -= alpha Ap over [first, first + stride, ...) of n elements and x += alpha p where the element lies in the x window
+// [row0, row0 + n_loc) (sliced vectors: the whole sweep); returns the thread's part of r.r.  ap_at(i) is element i of A p.
 // (axpby(alpha,p,1,x); axpby(-alpha,Ap,1,r); dot(r,r): ConjugateGradient_CPU_MPI_OMP.hpp:107-110)
+template <bool X_FIRST, typename TV, typename ApAt>
+__device__ __forceinline__ double sweep_xr(TV alpha, uint64_t first, uint64_t stride, uint64_t n, const TV *p, TV *x, TV *r,
+                                           uint64_t row0, uint64_t n_loc, ApAt ap_at)
+{
+    auto x_step = [&](uint64_t i) {
+        if (i >= row0 && i < row0 + n_loc) x[i - row0] = alpha * p[i] + x[i - row0];
+    };
+    double acc = 0.0;
+    for (uint64_t i = first; i < n; i += stride) {
+        if (X_FIRST) x_step(i);
+        const TV ri = -alpha * ap_at(i) + r[i];
+        r[i] = ri;
+        acc += (double)ri * (double)ri;
+        if (!X_FIRST) x_step(i);
+    }
+    return acc;
+}
+
+// beta = rr'/rr and the stop test sqrt(rr'/bb) < rel_error (ConjugateGradient_CPU_MPI_OMP.hpp:110-114: the test comes BEFORE the
+// p update).  Every workgroup reaches the same decision from the same bits; thread 0 of the leader workgroup records it.
+template <typename TV> struct CgDecision { bool stop; TV beta; };
+template <typename TV>
+__device__ __forceinline__ CgDecision<TV> cg_decide(CgScalars *sc, int k, double rr, double bb, double rr_new, double rel_error,
+                                                    volatile int *host_flags /* pinned host progress word, see post_progress */,
+                                                    bool leader_block /* the workgroup whose thread 0 keeps CgScalars */)
+{
+    const double beta_d = rr_new / rr;
+    const bool stop = sqrt(rr_new / bb) < rel_error;
+    if (leader_block && threadIdx.x == 0) {
+        sc->rr[k & 1] = rr_new;
+        sc->beta = beta_d;
+        sc->iters = k;
+        post_progress(host_flags, k, stop);   // WHICH iteration stopped: the host compares it with the iteration whose
+                                              // completion it has awaited (lam_hip_cg_iterate)
+        if (stop) sc->stop = 1;               // a workgroup that starts after the flag is up returns at the top: the same outcome
+    }
+    CgDecision<TV> d;
+    d.stop = stop;
+    d.beta = (TV)beta_d;
+    return d;
+}
+
+// p = r + beta p over [first, first + stride, ...) of n elements; store(i, p_i) puts the element where the caller keeps p
+template <typename TV, typename Store>
+__device__ __forceinline__ void sweep_p(TV beta, uint64_t first, uint64_t stride, uint64_t n, const TV *r, const TV *p, Store store)
+{
+    for (uint64_t i = first; i < n; i += stride) store(i, r[i] + beta * p[i]);
+}
+
+// sliced vectors: the p slice goes to [row0, row0 + n_loc) of every replica in pdst -- plain stores, or with the direct exchange
+// (post.n > 0) system-scope (write-through) stores, after which workgroup `block` raises its flag in every peer's mailbox
+template <typename TV>
+__device__ __forceinline__ void sweep_p_slice(TV beta, uint64_t first, uint64_t stride, uint64_t n_loc, const TV *r, const TV *p_loc,
+                                              const PtrList &pdst, uint64_t row0, const MailPost &post, int block)
+{
+    if (post.n == 0) {
+        sweep_p(beta, first, stride, n_loc, r, p_loc, [&](uint64_t i, TV pi) {
+            for (int j = 0; j < pdst.n; j++) reinterpret_cast<TV *>(pdst.p[j])[row0 + i] = pi;
+        });
+        return;
+    }
+    sweep_p(beta, first, stride, n_loc, r, p_loc, [&](uint64_t i, TV pi) {
+        for (int j = 0; j < pdst.n; j++)
+            __hip_atomic_store(reinterpret_cast<TV *>(pdst.p[j]) + row0 + i, pi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    });
+    // every thread: its slice stores happen-before the workgroup's flag stores (system-scope release fence, then the
+    // workgroup barrier, then relaxed flag stores; the reader pairs it with an acquire fence behind its poll)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if ((int)threadIdx.x < post.n && (int)threadIdx.x != post.rank)
+        st_sys(&post.mail[threadIdx.x]->pflag[post.rank][block], post.seq);
+}
+
+// alpha = rr / p.Ap ; x += alpha p ; r -= alpha Ap ; partials of r.r
 template <typename TV>
 __global__ void __launch_bounds__(kBlock)
 update_xr_kernel(const double *__restrict__ red, int nred, CgScalars *sc, int k,
@@ -1592,24 +1698,15 @@ update_xr_kernel(const double *__restrict__ red, int nred, CgScalars *sc, int k,
     if (sc->stop) return;
     if (is_reducer_block(fin)) { reduce_partials(partial, (int)gridDim.x - 1, fin, s_red); return; }
     const double pAp = mw.n > 0 ? mail_sum(mw, s_red) : block_sum_array(red, nred, s_red);
-    const double rr = sc->rr[(k + 1) & 1];
-    const double alpha_d = rr / pAp;
-    const TV alpha = (TV)alpha_d;
-    double acc = 0.0;
-    const uint64_t stride = (uint64_t)compute_blocks(fin) * kBlock;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n_loc; i += stride) {
-        x[i] = alpha * p_loc[i] + x[i];
-        const TV ri = -alpha * Ap[i] + r[i];
-        r[i] = ri;
-        acc += (double)ri * (double)ri;
-    }
+    const CgAlpha<TV> a = cg_alpha<TV>(sc, k, pAp);
+    const double acc = sweep_xr<true>(a.alpha, (uint64_t)blockIdx.x * kBlock + threadIdx.x, (uint64_t)compute_blocks(fin) * kBlock, n_loc,
+                                p_loc, x, r, 0, n_loc, [&](uint64_t i) { return Ap[i]; });
     double t = block_sum(acc, s_red);
-    if (threadIdx.x == 0 && blockIdx.x == 0) { sc->pAp = pAp; sc->alpha = alpha_d; }
+    if (threadIdx.x == 0 && blockIdx.x == 0) { sc->pAp = pAp; sc->alpha = a.alpha_d; }
     publish_partial(t, partial, fin);
 }
 
 // rr' = r.r ; beta = rr'/rr ; if sqrt(rr'/bb) < tol: stop (p untouched) else p_slice = r + beta p
-// (ConjugateGradient_CPU_MPI_OMP.hpp:110-114: the test comes BEFORE the p update)
 template <typename TV>
 __global__ void __launch_bounds__(kBlock)
 update_p_kernel(const double *__restrict__ red, int nred, CgScalars *sc, int k, double rel_error,
@@ -1622,43 +1719,10 @@ update_p_kernel(const double *__restrict__ red, int nred, CgScalars *sc, int k, 
     const double rr_new = mw.n > 0 ? mail_sum(mw, s_red) : block_sum_array(red, nred, s_red);
     const double rr = sc->rr[(k + 1) & 1];
     const double bb = sc->bb;
-    const double beta_d = rr_new / rr;
-    const bool stop = sqrt(rr_new / bb) < rel_error;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        sc->rr[k & 1] = rr_new;
-        sc->beta = beta_d;
-        sc->iters = k;
-        post_progress(host_flags, k, stop);   // WHICH iteration stopped: the host compares it with the iteration whose
-                                              // completion it has awaited (lam_hip_cg_iterate)
-    }
-    if (stop) {
-        // every workgroup reaches the same decision from the same bits; a workgroup that starts
-        // after the flag is up returns at the top, which is the same outcome (p is not updated)
-        if (blockIdx.x == 0 && threadIdx.x == 0) sc->stop = 1;
-        return;
-    }
-    const TV beta = (TV)beta_d;
-    if (post.n == 0) {
-        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n_loc; i += (uint64_t)gridDim.x * kBlock) {
-            const TV pi = r[i] + beta * p_loc[i];
-            for (int j = 0; j < pdst.n; j++) reinterpret_cast<TV *>(pdst.p[j])[row0 + i] = pi;
-        }
-        return;
-    }
-    // direct exchange: the slice goes into every rank's replica with system-scope (write-through) stores;
-    // once this workgroup's stores have drained it raises its flag in every mailbox
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n_loc; i += (uint64_t)gridDim.x * kBlock) {
-        const TV pi = r[i] + beta * p_loc[i];
-        for (int j = 0; j < pdst.n; j++)
-            __hip_atomic_store(reinterpret_cast<TV *>(pdst.p[j]) + row0 + i, pi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    // every thread: its slice stores happen-before the workgroup's flag stores (system-scope release fence, then the
-    // workgroup barrier, then relaxed flag stores; the reader pairs it with an acquire fence behind its poll)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if ((int)threadIdx.x < post.n && (int)threadIdx.x != post.rank)
-        st_sys(&post.mail[threadIdx.x]->pflag[post.rank][blockIdx.x], post.seq);
+    const CgDecision<TV> d = cg_decide<TV>(sc, k, rr, bb, rr_new, rel_error, host_flags, blockIdx.x == 0);
+    if (d.stop) return;
+    sweep_p_slice(d.beta, (uint64_t)blockIdx.x * kBlock + threadIdx.x, (uint64_t)gridDim.x * kBlock, n_loc, r, p_loc, pdst, row0, post,
+                  (int)blockIdx.x);
 }
 
 // direct exchange: wait until every other rank's update_p workgroups have flagged their p slice for `seq`
@@ -1697,6 +1761,7 @@ __device__ __forceinline__ void wait_p_flags(const Mail *mine, int nranks, int r
 // workgroups through a broadcast slot in ordinary device memory, which they poll (bounded) at agent scope.  All workgroups of the launch are resident
 // together (at most 256 + 2 of them), so nobody waits for a workgroup that cannot start.  Arithmetic, element
 // -> thread mapping and reduction order are those of the two kernels: results are bit-identical.
+// (The same helpers, that is; the first index of a sweep is cb-based here and the stride is ncompute workgroups.)
 // Roles by workgroup index: 0 reducer, [1, ncompute] compute, ncompute + 1 (direct exchange without
 // the own-slice GEMV panel only) the WAITER that holds the launch open until the peers' p slices for the next
 // GEMV have arrived -- which makes wait_p_kernel unnecessary: 2 launches per iteration.
@@ -1736,52 +1801,19 @@ update_fused_kernel(const double *__restrict__ red, int nred, CgScalars *sc, int
         wait_p_flags(mine, post.n, post.rank, nb, post.seq, host_err);
         return;
     }
-    // ---- update_xr_kernel
+    // ---- update_xr_kernel's part
     const double pAp = mw_pap.n > 0 ? bcast_wait(bc + cb, seq, host_err, s_red) : block_sum_array(red, nred, s_red);
-    const double rr = sc->rr[(k + 1) & 1];
-    const double alpha_d = rr / pAp;
-    const TV alpha = (TV)alpha_d;
-    double acc = 0.0;
-    const uint64_t stride = (uint64_t)ncompute * kBlock;
-    for (uint64_t i = (uint64_t)cb * kBlock + threadIdx.x; i < n_loc; i += stride) {
-        x[i] = alpha * p_loc[i] + x[i];
-        const TV ri = -alpha * Ap[i] + r[i];
-        r[i] = ri;
-        acc += (double)ri * (double)ri;
-    }
+    const CgAlpha<TV> a = cg_alpha<TV>(sc, k, pAp);
+    const uint64_t first = (uint64_t)cb * kBlock + threadIdx.x, stride = (uint64_t)ncompute * kBlock;
+    const double acc = sweep_xr<true>(a.alpha, first, stride, n_loc, p_loc, x, r, 0, n_loc, [&](uint64_t i) { return Ap[i]; });
     const double t = block_sum(acc, s_red);
-    if (threadIdx.x == 0 && cb == 0) { sc->pAp = pAp; sc->alpha = alpha_d; }
+    if (threadIdx.x == 0 && cb == 0) { sc->pAp = pAp; sc->alpha = a.alpha_d; }
     if (threadIdx.x == 0) __hip_atomic_store(partial + cb, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // ---- update_p_kernel
+    // ---- update_p_kernel's part
     const double rr_new = bcast_wait(bc + kBcastLines + cb, seq, host_err, s_red);
-    const double beta_d = rr_new / rr;
-    const bool stop = sqrt(rr_new / bb) < rel_error;
-    if (cb == 0 && threadIdx.x == 0) {
-        sc->rr[k & 1] = rr_new;
-        sc->beta = beta_d;
-        sc->iters = k;
-        post_progress(host_flags, k, stop);
-        if (stop) sc->stop = 1;
-    }
-    if (stop) return;
-    const TV beta = (TV)beta_d;
-    if (post.n == 0) {
-        for (uint64_t i = (uint64_t)cb * kBlock + threadIdx.x; i < n_loc; i += stride) {
-            const TV pi = r[i] + beta * p_loc[i];
-            for (int j = 0; j < pdst.n; j++) reinterpret_cast<TV *>(pdst.p[j])[row0 + i] = pi;
-        }
-        return;
-    }
-    for (uint64_t i = (uint64_t)cb * kBlock + threadIdx.x; i < n_loc; i += stride) {
-        const TV pi = r[i] + beta * p_loc[i];
-        for (int j = 0; j < pdst.n; j++)
-            __hip_atomic_store(reinterpret_cast<TV *>(pdst.p[j]) + row0 + i, pi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");        // as in update_p_kernel
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if ((int)threadIdx.x < post.n && (int)threadIdx.x != post.rank)
-        st_sys(&post.mail[threadIdx.x]->pflag[post.rank][cb], post.seq);
+    const CgDecision<TV> d = cg_decide<TV>(sc, k, a.rr, bb, rr_new, rel_error, host_flags, cb == 0);
+    if (d.stop) return;
+    sweep_p_slice(d.beta, first, stride, n_loc, r, p_loc, pdst, row0, post, cb);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -1844,6 +1876,15 @@ __device__ __forceinline__ TV gathered_ap(const char *__restrict__ gathered, uin
     return v;
 }
 
+// p.Ap out of the gathered records: the sum of their tails in rank order, the same on every rank
+__device__ __forceinline__ double gathered_pap(const char *__restrict__ gathered, uint64_t stride_bytes, int nranks)
+{
+    double pAp = 0.0;
+    for (int q = 0; q < nranks; q++)
+        pAp += *reinterpret_cast<const double *>(gathered + (uint64_t)q * stride_bytes + stride_bytes - 8);
+    return pAp;
+}
+
 template <typename TV>
 __global__ void __launch_bounds__(kBlock)
 update_xr_full_kernel(const char *__restrict__ gathered, uint64_t stride_bytes, uint64_t base, int nranks,
@@ -1852,24 +1893,14 @@ update_xr_full_kernel(const char *__restrict__ gathered, uint64_t stride_bytes, 
 {
     __shared__ double s_red[kWaves];
     if (sc->stop) return;
-    double pAp = 0.0;                                   // rank order, same on every rank
-    for (int q = 0; q < nranks; q++)
-        pAp += *reinterpret_cast<const double *>(gathered + (uint64_t)q * stride_bytes + stride_bytes - 8);
-    const double rr = sc->rr[(k + 1) & 1];
-    const double alpha_d = rr / pAp;
-    const TV alpha = (TV)alpha_d;
-    double acc = 0.0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const TV api = gathered_ap<TV>(gathered, stride_bytes, base, nranks, sum_records, i);
-        const TV ri = -alpha * api + r_full[i];
-        r_full[i] = ri;
-        acc += (double)ri * (double)ri;
-        if (i >= row0 && i < row0 + n_loc) x[i - row0] = alpha * p_full[i] + x[i - row0];
-    }
+    const double pAp = gathered_pap(gathered, stride_bytes, nranks);
+    const CgAlpha<TV> a = cg_alpha<TV>(sc, k, pAp);
+    const double acc = sweep_xr<false>(a.alpha, (uint64_t)blockIdx.x * kBlock + threadIdx.x, (uint64_t)gridDim.x * kBlock, n, p_full, x, r_full,
+                                row0, n_loc, [&](uint64_t i) { return gathered_ap<TV>(gathered, stride_bytes, base, nranks, sum_records, i); });
     double t = block_sum(acc, s_red);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = t;
-        if (blockIdx.x == 0) { sc->pAp = pAp; sc->alpha = alpha_d; }
+        if (blockIdx.x == 0) { sc->pAp = pAp; sc->alpha = a.alpha_d; }
     }
 }
 
@@ -1883,22 +1914,10 @@ update_p_full_kernel(const double *__restrict__ red, int nred, CgScalars *sc, in
     const double rr_new = block_sum_array(red, nred, s_red);
     const double rr = sc->rr[(k + 1) & 1];
     const double bb = sc->bb;
-    const double beta_d = rr_new / rr;
-    const bool stop = sqrt(rr_new / bb) < rel_error;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        sc->rr[k & 1] = rr_new;
-        sc->beta = beta_d;
-        sc->iters = k;
-        post_progress(host_flags, k, stop);   // WHICH iteration stopped: the host compares it with the iteration whose
-                                              // completion it has awaited (lam_hip_cg_iterate)
-    }
-    if (stop) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) sc->stop = 1;
-        return;
-    }
-    const TV beta = (TV)beta_d;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
-        p_full[i] = r_full[i] + beta * p_full[i];
+    const CgDecision<TV> d = cg_decide<TV>(sc, k, rr, bb, rr_new, rel_error, host_flags, blockIdx.x == 0);
+    if (d.stop) return;
+    sweep_p(d.beta, (uint64_t)blockIdx.x * kBlock + threadIdx.x, (uint64_t)gridDim.x * kBlock, n, r_full, (const TV *)p_full,
+            [&](uint64_t i, TV pi) { p_full[i] = pi; });
 }
 
 // update_xr_full_kernel + update_p_full_kernel in ONE launch (round 4): what separates them is the grid-wide r.r, which the
@@ -1922,41 +1941,21 @@ update_full_fused_kernel(const char *__restrict__ gathered, uint64_t stride_byte
         return;
     }
     const int cb = (int)blockIdx.x - 1;
-    double pAp = 0.0;                                   // rank order, same on every shard
-    for (int q = 0; q < nranks; q++)
-        pAp += *reinterpret_cast<const double *>(gathered + (uint64_t)q * stride_bytes + stride_bytes - 8);
-    const double rr = sc->rr[(k + 1) & 1];
+    const double pAp = gathered_pap(gathered, stride_bytes, nranks);
+    const CgAlpha<TV> a = cg_alpha<TV>(sc, k, pAp);
     const double bb = sc->bb;
-    const double alpha_d = rr / pAp;
-    const TV alpha = (TV)alpha_d;
-    double acc = 0.0;
-    const uint64_t stride = (uint64_t)ncompute * kBlock;
-    for (uint64_t i = (uint64_t)cb * kBlock + threadIdx.x; i < n; i += stride) {
-        const TV api = gathered_ap<TV>(gathered, stride_bytes, base, nranks, sum_records, i);
-        const TV ri = -alpha * api + r_full[i];
-        r_full[i] = ri;
-        acc += (double)ri * (double)ri;
-        if (i >= row0 && i < row0 + n_loc) x[i - row0] = alpha * p_full[i] + x[i - row0];
-    }
+    const uint64_t first = (uint64_t)cb * kBlock + threadIdx.x, stride = (uint64_t)ncompute * kBlock;
+    const double acc = sweep_xr<false>(a.alpha, first, stride, n, (const TV *)p_full, x, r_full, row0, n_loc,
+                                [&](uint64_t i) { return gathered_ap<TV>(gathered, stride_bytes, base, nranks, sum_records, i); });
     const double t = block_sum(acc, s_red);
     if (threadIdx.x == 0) {
         __hip_atomic_store(partial + cb, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cb == 0) { sc->pAp = pAp; sc->alpha = alpha_d; }
+        if (cb == 0) { sc->pAp = pAp; sc->alpha = a.alpha_d; }
     }
     const double rr_new = bcast_wait(bc + cb, seq, host_err, s_red);
-    const double beta_d = rr_new / rr;
-    const bool stop = sqrt(rr_new / bb) < rel_error;
-    if (cb == 0 && threadIdx.x == 0) {
-        sc->rr[k & 1] = rr_new;
-        sc->beta = beta_d;
-        sc->iters = k;
-        post_progress(host_flags, k, stop);
-        if (stop) sc->stop = 1;
-    }
-    if (stop) return;
-    const TV beta = (TV)beta_d;
-    for (uint64_t i = (uint64_t)cb * kBlock + threadIdx.x; i < n; i += stride)
-        p_full[i] = r_full[i] + beta * p_full[i];
+    const CgDecision<TV> d = cg_decide<TV>(sc, k, a.rr, bb, rr_new, rel_error, host_flags, cb == 0);
+    if (d.stop) return;
+    sweep_p(d.beta, first, stride, n, (const TV *)r_full, (const TV *)p_full, [&](uint64_t i, TV pi) { p_full[i] = pi; });
 }
 
 #ifdef LAM_TUNING_VARIANTS
@@ -2256,18 +2255,10 @@ cg_persist_kernel(PersistArgs<TA, TV> a)
 
         // ---- hand-over 2: r.r of this iteration, for everybody
         const double rr_new = persist_wait(a.bc_rr + w, seq, a.host_err, s_red);
-        const double beta_d = rr_new / rr_old;
-        const bool stop = sqrt(rr_new / bb) < a.rel_error;
-        if (w == 0 && tid == 0) {
-            a.sc->rr[k & 1] = rr_new;
-            a.sc->beta = beta_d;
-            a.sc->iters = k;
-            post_progress(a.host_flags, k, stop);
-            if (stop) a.sc->stop = 1;
-        }
-        if (stop) return;                              // like the two-launch form: p is not updated by the stopping iteration
+        const CgDecision<TV> d = cg_decide<TV>(a.sc, k, rr_old, bb, rr_new, a.rel_error, a.host_flags, w == 0);
+        if (d.stop) return;                            // like the two-launch form: p is not updated by the stopping iteration
         if (!(rr_new == rr_new)) return;               // a bounded wait expired somewhere (NaN total): the launch drains
-        beta = (TV)beta_d;
+        beta = d.beta;
         rr_old = rr_new;
     }
     // ---- leave the explicit p of the two-launch form behind: p_k = r_k + beta_k p_{k-1}
