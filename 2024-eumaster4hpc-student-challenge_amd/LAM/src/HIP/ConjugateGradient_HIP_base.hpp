@@ -287,6 +287,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         _batch_failed = true;
         if (!ensure_ctx()) return false;
         if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        if (!apply_shifts(nrhs, true)) return false;
         lam_hip_stats st;
         if (lam_hip_solve_many(_ctx, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0) return report("solve_many");
         _stats = st;
@@ -304,6 +305,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         _batch_failed = true;
         if (!ensure_ctx()) return false;
         if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        if (!apply_shifts(nrhs, true)) return false;
         lam_hip_stats st;
         if (lam_hip_solve_many_pc(_ctx, precond, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0)
             return report("solve_many_pc");
@@ -322,6 +324,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         _batch_failed = true;
         if (!ensure_ctx()) return false;
         if (B != nullptr && lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        if (!apply_shifts(nrhs, B != nullptr)) return false;
         lam_hip_stats st;
         if (lam_hip_solve_many_x0(_ctx, precond, X0, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0)
             return report("solve_many_x0");
@@ -330,6 +333,18 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         _batch_failed = false;
         return st.converged != 0;
     }
+    // Shifted systems (lam_hip_set_shifts_many): column j of the following solve_many* / true_residual_many calls is
+    // (A + sigma[j] I) x_j = b_j.  UNLIKE the C ABI, whose lam_hip_set_rhs_many clears the shifts, the class KEEPS them until
+    // set_shifts_many is called again (sigma == null or nrhs == 0 clears): its solve_many* members set the right-hand sides
+    // themselves, so shifts that died with them could never be used.  New shifts before a continuation (solve_many_x0 with B == null
+    // and X0 == null) follow the path from the previous shifts' solutions.  solve_many* and true_residual_many hand the shifts on
+    // (apply_shifts), so a program that instantiates any of them needs an ABI that has lam_hip_set_shifts_many.
+    void set_shifts_many(int nrhs, const double *sigma)
+    {
+        if (sigma != nullptr && nrhs > 0) _shifts.assign(sigma, sigma + nrhs);
+        else _shifts.clear();
+        _shifts_pending = true;
+    }
     bool batch_failed() const { return _batch_failed; }      // the last solve_many* / true_residual_many call returned an error
     // ||b_j - A x_j|| / ||b_j|| of the first nrhs columns of the last batched solution, one batched product
     // (lam_hip_true_residual_many); the solution stays readable and continuable
@@ -337,6 +352,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
     {
         _batch_failed = true;
         if (!ensure_ctx()) return false;
+        if (!apply_shifts(nrhs, false)) return false;
         if (lam_hip_true_residual_many(_ctx, nrhs, rel_res) != 0) return report("true_residual_many");
         _batch_failed = false;
         return true;
@@ -403,6 +419,16 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         fprintf(stderr, "LAM HIP: %s failed: %s\n", what, lam_hip_last_error(_ctx));
         return false;
     }
+    // The kept shifts reach the library when set_shifts_many changed them, or behind a lam_hip_set_rhs_many while some are kept (it
+    // cleared the library's); then they are set, or cleared if none are kept.
+    bool apply_shifts(int nrhs, bool rhs_reset)
+    {
+        if (!_shifts_pending && !(rhs_reset && !_shifts.empty())) return true;
+        _shifts_pending = false;
+        const bool none = _shifts.empty();
+        if (lam_hip_set_shifts_many(_ctx, none ? nrhs : (int)_shifts.size(), none ? nullptr : _shifts.data()) != 0) return report("set_shifts_many");
+        return true;
+    }
     static constexpr int dtype() { return std::is_same<FloatingType, double>::value ? LAM_HIP_F64 : LAM_HIP_F32; }
 
     mutable lam_hip_ctx *_ctx = nullptr;
@@ -414,6 +440,8 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
     bool _gemv_plus_comm = [] { const char *v = getenv("LAM_CSV_GEMV_PLUS_COMM"); return v && *v && *v != '0'; }();
     lam_hip_stats _stats{};
     bool _batch_failed = false;
+    std::vector<double> _shifts;      // set_shifts_many: empty = none
+    bool _shifts_pending = false;     // changed since they were last handed to the library
 };
 
 }  // namespace LAM

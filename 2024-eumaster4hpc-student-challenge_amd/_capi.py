@@ -131,6 +131,7 @@ def lib():
             "lam_hip_solve_many_x0": ([vp, i32, vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double)], i32),
             "lam_hip_true_residual_many": ([vp, i32, C.POINTER(C.c_double)], i32),
+            "lam_hip_set_shifts_many": ([vp, i32, C.POINTER(C.c_double)], i32),
             "lam_hip_get_diagonal": ([vp, vp], i32),
             "lam_hip_get_solution_many": ([vp, i32, vp], i32),
             "lam_hip_gemv_many": ([vp, i32, vp, vp], i32),
@@ -421,6 +422,26 @@ class Solver:
         B = self._as_columns(B)
         self._chk(self._L.lam_hip_set_rhs_many(self._h, B.shape[0], B.ctypes.data_as(C.c_void_p)))
         self.nrhs = B.shape[0]
+
+    def set_shifts(self, sigma):
+        """Column j of the following solve_many / true_residuals is (A + sigma[j] I) x_j = b_j (lam_hip_set_shifts_many): one finite
+        shift >= 0 per right-hand side of set_rhs_many, which clears them; None clears them too.  gemv_many stays A's product."""
+        k = getattr(self, "nrhs", 0)
+        if sigma is None:
+            self._chk(self._L.lam_hip_set_shifts_many(self._h, k, None))
+            return
+        sg = np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64)
+        assert sg.ndim == 1, "shifts are a list of nrhs numbers"
+        self._chk(self._L.lam_hip_set_shifts_many(self._h, sg.size, sg.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def solve_shifted(self, b, shifts, max_iters, rel_error, precond=PC_NONE, x0=None):
+        """(A + shifts[j] I) x_j = b for 1..MAX_RHS shifts in one batch: b replicated, set_shifts, solve_many.  Returns what
+        solve_many returns; solutions() and true_residuals() follow as usual."""
+        sg = np.atleast_1d(np.asarray(shifts, dtype=np.float64))
+        b = np.ascontiguousarray(b, dtype=self.vec_dtype).reshape(1, -1)
+        self.set_rhs_many(np.repeat(b, sg.size, axis=0))
+        self.set_shifts(sg)
+        return self.solve_many(max_iters, rel_error, precond, x0)
 
     def solve_many(self, max_iters, rel_error, precond=PC_NONE, x0=None):
         """Independent CG recurrences for the right-hand sides of set_rhs_many, one pass over the matrix per iteration.  Returns

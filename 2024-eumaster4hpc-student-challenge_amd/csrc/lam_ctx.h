@@ -103,6 +103,10 @@ struct MultiState {
     int nrhs = 0, K = 0;         // right-hand sides set / instantiation they are stored for
     bool have_rhs = false, solved = false;
     int last_K = 0;              // option "multi_rhs_k": the K the last batched call ran
+    // lam_hip_set_shifts_many: column j is the system (A + shift[j] I) x_j = b_j.  Each value is exactly a value of the vector dtype;
+    // shifted == some shift[j] != 0, and only then do the SHIFT instantiations run.  Cleared with the right-hand sides.
+    double shift[kMaxRhs] = {};
+    bool shifted = false;
 };
 
 // Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,
@@ -115,6 +119,15 @@ struct PcgState {
     uint64_t diag_gen = ~0ull;   // matrix_gen the diagonal was extracted from
     uint64_t bad_count = 0, bad_row = 0;     // what that extraction found (bad_count == 0: usable)
     double bad_value = 0.0;
+    // the shifted batch's K-wide reciprocal, dinv_k[i * K + j] = 1 / (A_ii + shift[j]) (shifted_dinv_kernel): built once per
+    // (matrix content, K, nrhs, shifts), which is the key below; kMaxRhs * n elements, allocated by the first shifted Jacobi solve
+    void *dinv_k = nullptr;
+    uint64_t dinvk_gen = ~0ull;
+    int dinvk_K = 0, dinvk_nrhs = 0;
+    double dinvk_shift[kMaxRhs] = {};
+    uint64_t badk_count = 0, badk_row = 0;
+    int badk_col = 0;
+    double badk_value = 0.0;
 };
 
 }  // namespace

@@ -2440,6 +2440,12 @@ pitch_copy_kernel(const TS *__restrict__ src, uint64_t src_pitch, TD *__restrict
 // statements, so on a matrix whose diagonal is a constant power of two every quantity is the plain recurrence's times an exact power
 // of two and x, the iteration counts and rel_err agree bit for bit.  With PC = false, dinv and the r.z partials are null and never
 // dereferenced.
+//
+// Shifted systems (lam_hip_set_shifts_many): column j solves (A + s_j I) x_j = b_j.  (A + s_j I) p_j = A p_j + s_j p_j, so the stream
+// of A is shared and the shift is one fma per (row, column) in the product's epilogue, compile-time SHIFT; AP then carries the shift
+// and the plain recurrence needs nothing else.  Under PC the preconditioner is M_j = diag(A) + s_j I: dinv becomes K-wide,
+// dinv[i * K + j], behind the compile-time DK of the three vector kernels (built and scanned by shifted_dinv_kernel).  SHIFT = false
+// and DK = false are the kernels of before, statement for statement.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxRhs = 8;
 constexpr int kMultiPadRows = 16;     // zero rows kept behind row n of a batched vector (>= the 8 elements of a bf16-sized vector)
@@ -2472,13 +2478,17 @@ struct MultiGemvArgs {
     double *partial;           // [K][nblocks]: column j's p_j.(A p_j) partial of workgroup b at [j * nblocks + b]; may be null
     const MultiScalars *sc;    // may be null; sc->all_stop: nothing to do
     uint64_t nrows, ncols, lda;
+    TV shift[kMaxRhs];         // SHIFT only: s_j of Y_j = (A + s_j I) P_j (lam_hip_set_shifts_many); last, so the others keep their offsets
 };
 
 // Y = A P for K vectors at once: the streaming body of gemv_coop_kernel (WAVES waves share R rows, 16-byte non-temporal loads of
 // the matrix, rotated tile start, zero-filled ragged tile + kZeroVec16 for the lanes past its end, fixed-order reductions) with K
 // accumulators per row: each 16-byte piece of a row is multiplied with the K values of p of each of its columns while it is in
 // registers.
-template <typename TA, typename TV, int K, int R, int WAVES, bool NT>
+// SHIFT (lam_hip_set_shifts_many): column j is the product of A + s_j I.  The stream is the same stream; the epilogue's one thread per
+// (row, column), which holds p_j[row] for the fused p_j.(A p_j), adds s_j p_j[row] with one fma in front of the store of y and of the
+// dot product, so both are the shifted matrix's.  SHIFT = false never reads a.shift.
+template <typename TA, typename TV, int K, int R, int WAVES, bool NT, bool SHIFT = false>
 __global__ void __launch_bounds__(WAVES * 64)
 multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
 {
@@ -2591,8 +2601,10 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
             TV s = s_part[tid][0];
 #pragma unroll
             for (int w = 1; w < WAVES; w++) s += s_part[tid][w];
+            const TV pj = a.p[row * K + j];
+            if constexpr (SHIFT) s = fma_tv(a.shift[j], pj, s);
             a.y[row * K + j] = s;
-            d = (double)s * (double)a.p[row * K + j];
+            d = (double)s * (double)pj;
         }
         s_dot[tid] = d;
     }
@@ -2613,7 +2625,8 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
 // R = B - AX rounded to the vector dtype, P = R (PC: dinv o R); b_j.b_j still goes to `partial`, r_j.r_j to partial_rr and r_j.z_j
 // to partial_rz.  r.r and r.z are accumulated by the statements, and so in the order, that take b.b and b.(dinv o b) without a
 // guess: with x0 = 0 (AX = 0, R = B exactly) their sums are those sums, bit for bit.
-template <typename TV, int K, bool PC, bool GUESS>
+// DK (PC only, the shifted batch): dinv is K-wide, dinv[i * K + j] = 1 / (A_ii + s_j), instead of one value per row.
+template <typename TV, int K, bool PC, bool GUESS, bool DK = false>
 __global__ void __launch_bounds__(kBlock)
 multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__ R, TV *__restrict__ P, uint64_t n,
                   double *__restrict__ partial, const TV *__restrict__ dinv, double *__restrict__ partial_rz,
@@ -2634,26 +2647,35 @@ multi_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__
     if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) P[n * K + threadIdx.x] = (TV)0;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
         [[maybe_unused]] TV di;
-        if constexpr (PC) di = dinv[i];
+        if constexpr (PC && !DK) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            TV bi = B[i * K + j];                // from here on r0's element: b's without a guess
+            uint64_t e = i * K + j;
+            // DK: the K-wide row of dinv would be K more live values next to the rows of B, AX and P, and cost waves at K = 8.  The
+            // column's index is made opaque and the columns are kept apart, so the row is met one column at a time and the K-wide
+            // instantiations keep the occupancy of their shared-dinv counterparts (one launch per solve: its latency is no matter)
+            // This leans on the compiler's scheduling: re-check DESIGN §11's table with -Rpass-analysis=kernel-resource-usage when the
+            // compiler changes (the worst case is a one-shot launch at lower occupancy, not a wrong result)
+            if constexpr (PC && DK) asm volatile("" : "+v"(e));
+            if constexpr (PC && DK) di = dinv[e];
+            TV bi = B[e];                        // from here on r0's element: b's without a guess
             if constexpr (GUESS) {
                 accb[j] += (double)bi * (double)bi;
-                X[i * K + j] = P[i * K + j];
-                bi = bi - AX[i * K + j];
+                X[e] = P[e];
+                bi = bi - AX[e];
             } else {
-                X[i * K + j] = (TV)0;
+                X[e] = (TV)0;
             }
-            R[i * K + j] = bi;
+            R[e] = bi;
             if constexpr (PC) {
                 const TV zi = di * bi;
-                P[i * K + j] = zi;
+                P[e] = zi;
                 accz[j] += (double)bi * (double)zi;
             } else {
-                P[i * K + j] = bi;
+                P[e] = bi;
             }
             acc[j] += (double)bi * (double)bi;
+            if constexpr (PC && DK) __builtin_amdgcn_sched_barrier(0);
         }
     }
 #pragma unroll
@@ -2765,7 +2787,7 @@ multi_residual_scalars_kernel(const double *__restrict__ red_rr, const double *_
 // per live, running column j: alpha_j = rr_j / p_j.Ap_j (PC: rz_j / p_j.Ap_j) ; x_j += alpha_j p_j ; r_j -= alpha_j Ap_j ; partials
 // of r_j.r_j (PC: and of r_j.(dinv o r_j))
 // (update_xr_kernel's statements, column by column; a stopped column is not read and not written)
-template <typename TV, int K, bool PC>
+template <typename TV, int K, bool PC, bool DK = false>
 __global__ void __launch_bounds__(kBlock)
 multi_xr_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int k, const TV *__restrict__ P, const TV *__restrict__ AP,
                 TV *__restrict__ X, TV *__restrict__ R, uint64_t n, double *__restrict__ partial, const TV *__restrict__ dinv,
@@ -2789,11 +2811,12 @@ multi_xr_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int 
     }
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
         [[maybe_unused]] TV di;
-        if constexpr (PC) di = dinv[i];
+        if constexpr (PC && !DK) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
             if (!run[j]) continue;
             const uint64_t e = i * K + j;
+            if constexpr (PC && DK) di = dinv[e];
             X[e] = alpha[j] * P[e] + X[e];
             const TV ri = -alpha[j] * AP[e] + R[e];
             R[e] = ri;
@@ -2824,7 +2847,7 @@ multi_xr_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int 
 // as stopped and leaves p_j alone, which is what it would have decided itself from the same bits (update_p_kernel's argument).
 // The PC p statement is an explicit fma(beta, p, z) with z = dinv o r rounded on its own: the plain r + beta p contracts to
 // fma(beta, p, r), and z must not be the operand that is fused (fma(dinv, r, beta p) rounds differently).
-template <typename TV, int K, bool PC>
+template <typename TV, int K, bool PC, bool DK = false>
 __global__ void __launch_bounds__(kBlock)
 multi_p_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int k, double rel_error, const TV *__restrict__ R,
                TV *__restrict__ P, uint64_t n, volatile int *host_flags, const TV *__restrict__ dinv,
@@ -2875,11 +2898,12 @@ multi_p_kernel(const double *__restrict__ red, int nred, BatchScalars *sc, int k
     if (all) return;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
         [[maybe_unused]] TV di;
-        if constexpr (PC) di = dinv[i];
+        if constexpr (PC && !DK) di = dinv[i];
 #pragma unroll
         for (int j = 0; j < K; j++) {
             if (!upd[j]) continue;
             const uint64_t e = i * K + j;
+            if constexpr (PC && DK) di = dinv[e];
             if constexpr (PC) {
                 const TV zi = di * R[e];
                 P[e] = fma_tv(beta[j], P[e], zi);
@@ -2937,6 +2961,36 @@ diag_extract_kernel(const TA *__restrict__ A, uint64_t lda, uint64_t row0, uint6
         if (!ok && info != nullptr) {
             atomicMin(&info->first_bad, (unsigned long long)(row0 + i));
             atomicAdd(&info->count, 1ull);
+        }
+    }
+}
+
+
+// by-value shifts of shifted_dinv_kernel, fp64 as the host keeps them (each exactly a value of the vector dtype)
+struct ShiftList { double s[kMaxRhs]; };
+
+// The Jacobi preconditioner of the shifted batch, M_j = diag(A) + s_j I: dinv[i * K + j] = 1 / ((double)A_ii + s_j), computed in fp64
+// and rounded to the vector dtype, for the nrhs live columns; the padding columns get 0 (their b, r and p are zero and stay so).
+// The scan is diag_extract_kernel's, on the SUM: info->first_bad is the smallest i * K + j whose sum or reciprocal is not finite and
+// > 0 in the vector dtype, so a zero on A's own diagonal passes where the shift lifts it.
+template <typename TA, typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+shifted_dinv_kernel(const TA *__restrict__ A, uint64_t lda, uint64_t nrows, int nrhs, ShiftList shift, TV *__restrict__ dinv,
+                    DiagInfo *info)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nrows; i += (uint64_t)gridDim.x * kBlock) {
+        const double a = (double)widen<TV>(A[i * lda + i]);
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (j >= nrhs) { dinv[i * K + j] = (TV)0; continue; }
+            const TV m = (TV)(a + shift.s[j]);
+            const TV inv = (TV)(1.0 / (a + shift.s[j]));
+            dinv[i * K + j] = inv;
+            const bool ok = m > (TV)0 && m <= std::numeric_limits<TV>::max() && inv > (TV)0 && inv <= std::numeric_limits<TV>::max();
+            if (!ok) {
+                atomicMin(&info->first_bad, (unsigned long long)(i * K + j));
+                atomicAdd(&info->count, 1ull);
+            }
         }
     }
 }

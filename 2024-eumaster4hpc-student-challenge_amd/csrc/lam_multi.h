@@ -1,5 +1,5 @@
-// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _solve_many / _solve_many_pc / _solve_many_x0 /
-// _true_residual_many / _get_solution_many / _gemv_many / _gemv_many_only, and lam_hip_get_diagonal.  nrhs independent CG recurrences (NOT block CG) advanced together, one
+// lam_multi.h -- several right-hand sides on one matrix: lam_hip_set_rhs_many / _set_shifts_many / _solve_many / _solve_many_pc /
+// _solve_many_x0 / _true_residual_many / _get_solution_many / _gemv_many / _gemv_many_only, and lam_hip_get_diagonal.  nrhs independent CG recurrences (NOT block CG) advanced together, one
 // pass over the matrix per iteration.
 // Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 //
@@ -11,6 +11,10 @@
 // One recurrence in the source: lam_hip_solve_many_pc(JACOBI) runs the PC = true instantiations of the same four vector kernels
 // (multi_init_kernel, multi_init_scalars_kernel, multi_xr_kernel, multi_p_kernel) on the same scalars' block, and
 // lam_hip_solve_many_x0 the GUESS = true instantiations of the two init kernels behind one more product launch; the loop is shared.
+// lam_hip_set_shifts_many makes column j the system (A + s_j I) x_j = b_j: the SHIFT = true instantiation of the product (its epilogue
+// adds s_j p_j[row]; the K shifts travel by value in its arguments) in the loop, in the guess's product and in the true residual's, and
+// under Jacobi the DK = true instantiations of the vector kernels on a K-wide dinv_k = 1 / (A_ii + s_j) (shifted_dinv_kernel).  No
+// shifts, or all of them zero: the instantiations and the launches of before.
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
@@ -25,13 +29,19 @@ void free_dev(std::initializer_list<void *> ptrs)
     for (void *q : ptrs) if (q) (void)hipFree(q);
 }
 
+void multi_clear_shifts(MultiState &m)
+{
+    for (double &v : m.shift) v = 0.0;
+    m.shifted = false;
+}
+
 void multi_release(lam_hip_ctx *c)
 {
     MultiState &m = c->multi;
     if (m.n == 0) return;        // the preconditioner's state is allocated behind the batch's only (pcg_ensure)
     if (c->sh.empty() || hipSetDevice(c->sh[0].dev) != hipSuccess) { (void)hipGetLastError(); return; }
     if (c->sh[0].stream) (void)hipStreamSynchronize(c->sh[0].stream);
-    free_dev({c->pcg.diag, c->pcg.dinv, c->pcg.part_rz, c->pcg.info});
+    free_dev({c->pcg.diag, c->pcg.dinv, c->pcg.dinv_k, c->pcg.part_rz, c->pcg.info});
     c->pcg = PcgState();
     free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.part_rr, m.res, m.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
@@ -130,17 +140,35 @@ int multi_dispatch(lam_hip_ctx *c, int K, bool pc, bool guess, F &&f)
 
 int multi_gemv_grid(const lam_hip_ctx *c) { return (int)((c->n + kMultiRows - 1) / kMultiRows); }
 
+// shift: null for the plain product of A (lam_hip_gemv_many*, and a batch without shifts: the SHIFT = false instantiation, the only
+// one there was), else the K shifts of the batch (MultiState::shift): Y_j = (A + s_j I) P_j
 template <typename TA, typename TV, int K>
-int multi_launch_gemv(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const MultiScalars *sc)
+int multi_launch_gemv(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const MultiScalars *sc, const double *shift = nullptr)
 {
     ShardBase &s = c->sh[0];
     MultiGemvArgs<TA, TV> a;
     a.A = (const TA *)s.A; a.p = P; a.y = Y; a.partial = partial; a.sc = sc;
     a.nrows = c->n; a.ncols = c->ncols_vec(); a.lda = c->lda;
-    hipLaunchKernelGGL((multi_gemv_kernel<TA, TV, K, kMultiRows, kMultiWaves, true>), dim3(multi_gemv_grid(c)), dim3(kMultiWaves * 64), 0,
-                       s.stream, a);
+    for (int j = 0; j < kMaxRhs; j++) a.shift[j] = shift ? (TV)shift[j] : (TV)0;
+    if (shift)
+        hipLaunchKernelGGL((multi_gemv_kernel<TA, TV, K, kMultiRows, kMultiWaves, true, true>), dim3(multi_gemv_grid(c)),
+                           dim3(kMultiWaves * 64), 0, s.stream, a);
+    else
+        hipLaunchKernelGGL((multi_gemv_kernel<TA, TV, K, kMultiRows, kMultiWaves, true>), dim3(multi_gemv_grid(c)), dim3(kMultiWaves * 64), 0,
+                           s.stream, a);
     LAUNCHED(c);
     return 0;
+}
+
+// and with the preconditioner's layout: f(..., bool_constant<PC>(), bool_constant<GUESS>(), bool_constant<DK>()), DK = K-wide dinv of
+// the shifted batch; only PC has such instantiations
+template <typename F>
+int multi_dispatch(lam_hip_ctx *c, int K, bool pc, bool guess, bool dk, F &&f)
+{
+    return multi_dispatch(c, K, pc, guess, [&](auto impl, auto k, auto pct, auto gt) -> int {
+        if constexpr (decltype(pct)::value) return dk ? f(impl, k, pct, gt, std::true_type()) : f(impl, k, pct, gt, std::false_type());
+        else return f(impl, k, pct, gt, std::false_type());
+    });
 }
 
 // host layout (column j contiguous at host + j * n) -> interleaved device vector `dst` of instantiation K, padding columns zero
@@ -193,7 +221,7 @@ int pcg_ensure(lam_hip_ctx *c)
     PcgState &g = c->pcg;
     if (g.info) return 0;
     LAMCHK(set_dev(c, c->sh[0]));
-    free_dev({g.diag, g.dinv, g.part_rz});      // what a failed attempt left: it is retried, never launched on
+    free_dev({g.diag, g.dinv, g.dinv_k, g.part_rz});      // what a failed attempt left: it is retried, never launched on
     g = PcgState();
     HIPCHK(c, hipMalloc(&g.diag, c->n * c->esz_v()));
     HIPCHK(c, hipMalloc(&g.dinv, c->n * c->esz_v()));
@@ -238,6 +266,52 @@ int pcg_extract_diagonal(lam_hip_ctx *c)
     return 0;
 }
 
+// dinv_k of the shifted batch, M_j = diag(A) + s_j I: one launch builds and scans it, once per (matrix content, K, nrhs, shifts).
+// The host reads the count and the first (row, column) that cannot be inverted, and for the message that row's one diagonal element.
+int pcg_build_shifted(lam_hip_ctx *c)
+{
+    PcgState &g = c->pcg;
+    MultiState &m = c->multi;
+    if (g.dinvk_gen == c->matrix_gen && g.dinvk_K == m.K && g.dinvk_nrhs == m.nrhs && !memcmp(g.dinvk_shift, m.shift, sizeof m.shift))
+        return 0;
+    ShardBase &s = c->sh[0];
+    g.dinvk_gen = ~0ull;
+    // K times the shared dinv: allocated by the first shifted Jacobi solve only, released with the rest (multi_release)
+    if (!g.dinv_k) HIPCHK(c, hipMalloc(&g.dinv_k, c->n * kMaxRhs * c->esz_v()));
+    DiagInfo h;
+    h.first_bad = ~0ull; h.count = 0;
+    HIPCHK(c, hipMemcpyAsync(g.info, &h, sizeof h, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));      // h is pageable
+    ShiftList sl;
+    for (int j = 0; j < kMaxRhs; j++) sl.s[j] = m.shift[j];
+    LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc) -> int {
+        using TA = typename ImplTraits<decltype(impl)>::TA;
+        using TV = typename ImplTraits<decltype(impl)>::TV;
+        hipLaunchKernelGGL((shifted_dinv_kernel<TA, TV, decltype(kc)::value>), dim3(vec_grid(c->n)), dim3(kBlock), 0, s.stream,
+                           (const TA *)s.A, c->lda, c->n, m.nrhs, sl, (TV *)g.dinv_k, g.info);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }));
+    HIPCHK(c, hipMemcpyAsync(&h, g.info, sizeof h, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    g.badk_count = h.count;
+    g.badk_row = 0; g.badk_col = 0; g.badk_value = 0.0;
+    if (h.count != 0 && h.first_bad / m.K < c->n) {
+        g.badk_row = h.first_bad / m.K;
+        g.badk_col = (int)(h.first_bad % m.K);
+        double v64 = 0.0;
+        float v32 = 0.f;
+        void *dst = c->dtype == LAM_HIP_F64 ? (void *)&v64 : (void *)&v32;
+        HIPCHK(c, hipMemcpy(dst, (const char *)s.A + (g.badk_row * c->lda + g.badk_row) * c->esz_a(), c->esz_a(), hipMemcpyDeviceToHost));
+        const double sum = (c->dtype == LAM_HIP_F64 ? v64 : (double)v32) + m.shift[g.badk_col];
+        g.badk_value = c->dtype == LAM_HIP_F64 ? sum : (double)(float)sum;
+    }
+    g.dinvk_gen = c->matrix_gen;
+    g.dinvk_K = m.K; g.dinvk_nrhs = m.nrhs;
+    memcpy(g.dinvk_shift, m.shift, sizeof m.shift);
+    return 0;
+}
+
 void multi_harvest(MultiState &m, int slot, double *ms_sum, int *samples)
 {
     if (!m.timed_slot[slot]) return;
@@ -262,11 +336,39 @@ int lam_hip_set_rhs_many(lam_hip_ctx *c, int nrhs, const void *b_host)
     LAMCHK(multi_ensure(c));
     MultiState &m = c->multi;
     m.have_rhs = m.solved = false;
+    multi_clear_shifts(m);
     const int K = multi_k_for(nrhs);
     LAMCHK(multi_upload(c, nrhs, K, b_host, m.B));
     HIPCHK(c, hipStreamSynchronize(c->sh[0].stream));
     m.nrhs = nrhs; m.K = K;
     m.have_rhs = true;
+    return 0;
+}
+
+// No launch and no device traffic: the shifts travel by value in the product's arguments.  The batched solution, if there is one,
+// stays readable and lam_hip_solve_many_x0(..., NULL, ...) continues from it under the new shifts.
+int lam_hip_set_shifts_many(lam_hip_ctx *c, int nrhs, const double *sigma)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    LAMCHK(multi_supported(c, "lam_hip_set_shifts_many"));
+    LAMCHK(multi_check_nrhs(c, "lam_hip_set_shifts_many", nrhs));
+    MultiState &m = c->multi;
+    if (!m.have_rhs || m.n != c->n)
+        return fail(c, LAM_HIP_ESTATE, "right-hand sides (lam_hip_set_rhs_many) must be set before lam_hip_set_shifts_many");
+    if (nrhs != m.nrhs) return fail(c, LAM_HIP_EINVAL, "lam_hip_set_shifts_many: nrhs = %d, but %d right-hand sides are set", nrhs, m.nrhs);
+    if (!sigma) { multi_clear_shifts(m); return 0; }
+    double s[kMaxRhs] = {};
+    bool any = false;
+    for (int j = 0; j < nrhs; j++) {
+        const double r = c->dtype == LAM_HIP_F32 ? (double)(float)sigma[j] : sigma[j];
+        if (!(sigma[j] >= 0.0) || !std::isfinite(r))
+            return fail(c, LAM_HIP_EINVAL, "lam_hip_set_shifts_many: shift %d is %g: every shift must be finite and >= 0, in the vector "
+                        "dtype too", j, sigma[j]);
+        s[j] = r;
+        any = any || r != 0.0;
+    }
+    memcpy(m.shift, s, sizeof s);
+    m.shifted = any;
     return 0;
 }
 
@@ -302,7 +404,16 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     PcgState &g = c->pcg;
     m.solved = false;            // whatever follows, a refusal of the diagonal included, leaves no batched solution behind
-    if (pc) {
+    const bool dk = pc && m.shifted;             // M_j = diag(A) + s_j I: the K-wide reciprocal
+    const double *const shift = m.shifted ? m.shift : nullptr;
+    if (dk) {
+        LAMCHK(pcg_ensure(c));
+        LAMCHK(pcg_build_shifted(c));
+        if (g.badk_count != 0)
+            return fail(c, LAM_HIP_EINVAL, "%s: the Jacobi preconditioner needs A[i][i] + shift[j] and its reciprocal finite and > 0: "
+                        "row %llu, column %d holds %g (%llu such elements)", fn, (unsigned long long)g.badk_row, g.badk_col, g.badk_value,
+                        (unsigned long long)g.badk_count);
+    } else if (pc) {
         LAMCHK(pcg_ensure(c));
         LAMCHK(pcg_extract_diagonal(c));
         if (g.bad_count != 0)
@@ -321,21 +432,22 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
     int samples = 0, enq = 0;
     if (guess == kGuessHost) LAMCHK(multi_upload(c, m.nrhs, m.K, x0_host, m.P));
     if (guess == kGuessCurrent) LAMCHK(multi_stage_solution(c, m.K));
-    LAMCHK(multi_dispatch(c, m.K, pc, guess != kGuessNone, [&](auto impl, auto kc, auto pct, auto gt) -> int {
+    LAMCHK(multi_dispatch(c, m.K, pc, guess != kGuessNone, dk, [&](auto impl, auto kc, auto pct, auto gt, auto dkt) -> int {
         using I = decltype(impl);
         using TA = typename ImplTraits<I>::TA;
         using TV = typename ImplTraits<I>::TV;
         constexpr int K = decltype(kc)::value;
         constexpr bool PC = decltype(pct)::value;
         constexpr bool GUESS = decltype(gt)::value;
-        const TV *const dinv = PC ? (const TV *)g.dinv : nullptr;
+        constexpr bool DK = decltype(dkt)::value;
+        const TV *const dinv = PC ? (const TV *)(DK ? g.dinv_k : g.dinv) : nullptr;
         double *const part_rz = PC ? g.part_rz : nullptr;
         double *const part_rr = GUESS ? m.part_rr : nullptr;
-        // GUESS: AP = A x0 of the guess staged in P, outside the iteration's scalars and partials
-        if (GUESS) LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr)));
+        // GUESS: AP = A x0 ((A + s_j I) x0 of a shifted batch) of the guess staged in P, outside the iteration's scalars and partials
+        if (GUESS) LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr, shift)));
         // x = 0, r = b, p = b, bb_j = b_j.b_j  (PC: p = dinv o b, rz_j = b_j.(dinv o b_j));  GUESS: x = x0, r = b - A x0, p = r,
         // rr_j = r_j.r_j next to bb_j  (PC: p = dinv o r, rz_j = r_j.(dinv o r_j))
-        hipLaunchKernelGGL((multi_init_kernel<TV, K, PC, GUESS>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X,
+        hipLaunchKernelGGL((multi_init_kernel<TV, K, PC, GUESS, DK>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, (TV *)m.X,
                            (TV *)m.R, (TV *)m.P, c->n, m.part_vec, dinv, part_rz, (const TV *)(GUESS ? m.AP : nullptr), part_rr);
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL((multi_init_scalars_kernel<K, PC, GUESS>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb,
@@ -353,12 +465,12 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
             const bool timed = timed_iteration(c, s0, k);
             m.timed_slot[slot] = timed;
             if (timed) RECORD(c, m.ev0[slot], s0.stream);
-            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, m.sc)));
+            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, m.part_gemv, m.sc, shift)));
             if (timed) RECORD(c, m.ev1[slot], s0.stream);
-            hipLaunchKernelGGL((multi_xr_kernel<TV, K, PC>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
+            hipLaunchKernelGGL((multi_xr_kernel<TV, K, PC, DK>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, m.sc, k,
                                (const TV *)m.P, (const TV *)m.AP, (TV *)m.X, (TV *)m.R, c->n, m.part_vec, dinv, part_rz);
             LAUNCHED(c);
-            hipLaunchKernelGGL((multi_p_kernel<TV, K, PC>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k,
+            hipLaunchKernelGGL((multi_p_kernel<TV, K, PC, DK>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k,
                                rel_error, (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags, dinv, (const double *)part_rz);
             LAUNCHED(c);
             c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
@@ -452,7 +564,7 @@ int lam_hip_true_residual_many(lam_hip_ctx *c, int nrhs, double *rel_res)
         using TA = typename ImplTraits<I>::TA;
         using TV = typename ImplTraits<I>::TV;
         constexpr int K = decltype(kc)::value;
-        LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr)));
+        LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr, m.shifted ? m.shift : nullptr)));
         hipLaunchKernelGGL((multi_residual_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s.stream, (const TV *)m.B, (const TV *)m.AP, c->n,
                            m.part_rr, m.part_vec);
         HIPCHK(c, hipGetLastError());

@@ -1,17 +1,21 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
-//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
 // for the remaining max_iters - W; num_iters is the two stages' sum, rel_err the second stage's.
 // -T: each column's true residual ||b - A x|| / ||b|| (lam_hip_true_residual_many) as one more CSV column behind t_cg.
-// Without the two flags the calls and the output are those of the driver before them.
+// -S s0,s1,...: 1 to 8 shifts >= 0 (lam_hip_set_shifts_many); they set nrhs, column j is (A + s_j I) x_j = b_j with the SAME
+// right-hand side in every column (constant 1), and the shift is one more CSV column at the end of the line.  With -J the
+// preconditioner is diag(A) + s_j I; with -w the second stage continues under the same shifts; -T measures against them.
+// Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
 //     rows,procs,threads,t_load,t_comm_init,t_gemv,t_iter,num_iters,rel_err,t_cg
 // t_gemv / t_iter / t_cg are the batch's (the columns share every launch); num_iters and rel_err are the column's own.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +27,7 @@
 #include "LAM.hpp"
 
 template <typename T>
-static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi, int warm, bool true_res)
+static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi, int warm, bool true_res, const std::vector<double> &shifts)
 {
     using clk = std::chrono::high_resolution_clock;
     LAM::ConjugateGradient_HIP<T> cg(0);
@@ -36,7 +40,8 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
     const double t_load = std::chrono::duration<double>(clk::now() - t0).count();
     std::vector<T> B((size_t)nrhs * rows);
     for (int j = 0; j < nrhs; j++)
-        for (size_t i = 0; i < rows; i++) B[(size_t)j * rows + i] = (T)(double)(1u << j);
+        for (size_t i = 0; i < rows; i++) B[(size_t)j * rows + i] = shifts.empty() ? (T)(double)(1u << j) : (T)1;
+    if (!shifts.empty()) cg.set_shifts_many(nrhs, shifts.data());
     std::vector<int32_t> iters(nrhs), conv(nrhs);
     std::vector<double> rel(nrhs);
     const auto t1 = clk::now();
@@ -66,9 +71,26 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
         std::cout << rows << "," << 1 << "," << 1 << "," << t_load << "," << st.t_comm_init << "," << st.t_gemv << "," << st.t_iter << ","
                   << iters[j] << "," << rel[j] << "," << t_cg;
         if (true_res) std::cout << "," << tres[j];
+        if (!shifts.empty()) std::cout << "," << shifts[j];
         std::cout << std::endl;
     }
     return 0;
+}
+
+// "s0,s1,...": 1..LAM_HIP_MAX_RHS numbers, each finite and >= 0, nothing else in the list
+static bool parse_shifts(const char *arg, std::vector<double> *out)
+{
+    out->clear();
+    const char *p = arg;
+    for (;;) {
+        char *end = nullptr;
+        const double v = strtod(p, &end);
+        if (end == p || !(v >= 0.0) || !std::isfinite(v) || out->size() == (size_t)LAM_HIP_MAX_RHS) return false;
+        out->push_back(v);
+        if (*end == '\0') return true;
+        if (*end != ',') return false;
+        p = end + 1;
+    }
 }
 
 int main(int argc, char **argv)
@@ -79,30 +101,38 @@ int main(int argc, char **argv)
     const char *precision = "f64";
     bool jacobi = false, true_res = false;
     int warm = -1;                  // -1: no -w
-    bool bad_warm = false;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:Th")) != -1) {
+    bool bad_warm = false, bad_shifts = false, k_given = false;
+    std::vector<double> shifts;
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:h")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
-        case 'k': nrhs = atoi(optarg); break;
+        case 'k': nrhs = atoi(optarg); k_given = true; break;
         case 'i': max_iters = atoi(optarg); break;
         case 'e': rel_error = atof(optarg); break;
         case 't': precision = optarg; break;
         case 'J': jacobi = true; break;
         case 'w': warm = atoi(optarg); bad_warm = warm < 0; break;
         case 'T': true_res = true; break;
+        case 'S': bad_shifts = !parse_shifts(optarg, &shifts); break;
         default:
             fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
-                    "[-T (true residuals)]\n", argv[0]);
+                    "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)]\n", argv[0],
+                    LAM_HIP_MAX_RHS);
             return opt == 'h' ? 0 : 1;
         }
     }
+    if (bad_shifts || (!shifts.empty() && k_given && nrhs != (int)shifts.size())) {
+        fprintf(stderr, "-S takes 1..%d comma-separated finite shifts >= 0, and -k, if given, their number\n", LAM_HIP_MAX_RHS);
+        return 1;
+    }
+    if (!shifts.empty()) nrhs = (int)shifts.size();
     if (rows == 0 || nrhs < 1 || nrhs > LAM_HIP_MAX_RHS || max_iters < 0 || bad_warm || warm > max_iters) {
-        fprintf(stderr, "Usage: %s -s N -k nrhs (1..%d) -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (0..max_iters)] [-T]\n",
+        fprintf(stderr, "Usage: %s -s N -k nrhs (1..%d) -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (0..max_iters)] [-T] [-S s0,s1,...]\n",
                 argv[0], LAM_HIP_MAX_RHS);
         return 1;
     }
-    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res);
-    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res);
+    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts);
+    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts);
     fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
     return 1;
 }

@@ -49,7 +49,8 @@ extern "C" {
  *      "multi_rhs_k".  A caller that needs them checks for the symbols (dlsym) or the build id; the version number does not move.
  *      Added under version 4 likewise (purely additive): LAM_HIP_PC_NONE, LAM_HIP_PC_JACOBI, lam_hip_solve_many_pc and
  *      lam_hip_get_diagonal.
- *      Added under version 4 likewise (purely additive): lam_hip_solve_many_x0 and lam_hip_true_residual_many. */
+ *      Added under version 4 likewise (purely additive): lam_hip_solve_many_x0 and lam_hip_true_residual_many.
+ *      Added under version 4 likewise (purely additive): lam_hip_set_shifts_many. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -295,6 +296,32 @@ int lam_hip_solve_many_x0(lam_hip_ctx *ctx, int precond, const void *x0_host, in
  * batched solution: LAM_HIP_ESTATE.  B and X are left alone: the solution stays readable and a following
  * lam_hip_solve_many_x0(..., NULL, ...) continues from it.  Independent of the single-vector state, as all batch calls are. */
 int lam_hip_true_residual_many(lam_hip_ctx *ctx, int nrhs, double *rel_res);
+/* Shifted systems: from here on column j of every lam_hip_solve_many, _solve_many_pc, _solve_many_x0 and
+ * lam_hip_true_residual_many is the system (A + s_j I) x_j = b_j with s_j = sigma[j] rounded to the vector dtype -- a ridge /
+ * Tikhonov sweep, a noise-level scan, implicit time steps of different length: eight different matrices for the passes over A of
+ * one.  The product launch adds s_j p_j[row] in its epilogue (one fma per row and column, outside the stream of A), so A p, the
+ * fused p.(A p), the guess's A x0 and the true residual's A x are the shifted matrix's; nothing else in the recurrence changes.
+ * lam_hip_gemv_many and lam_hip_gemv_many_only stay the plain product of A.
+ *   - call it after lam_hip_set_rhs_many (else LAM_HIP_ESTATE) with the nrhs set there (else LAM_HIP_EINVAL); sigma == NULL
+ *     clears the shifts.  Every sigma[j] must be finite and >= 0, and finite after rounding to the vector dtype: a negative shift
+ *     can make the matrix indefinite, for which CG is the wrong method.  Anything else: LAM_HIP_EINVAL, the message names the
+ *     column and the value, and the shifts in force stay.  It refuses what the batch refuses (several shards, rank mode,
+ *     LAM_HIP_BF16) with the same codes and words;
+ *   - lam_hip_set_rhs_many and lam_hip_set_problem clear the shifts: a caller that never heard of them is unaffected;
+ *   - new shifts do NOT invalidate the batched solution: lam_hip_solve_many_x0(..., NULL, ...) after lam_hip_set_shifts_many
+ *     continues from the previous shifts' solutions (path-following along a regularisation path), and
+ *     lam_hip_true_residual_many measures against the shifts in force;
+ *   - no shifts, or every s_j == 0 after rounding: the unshifted kernels run and every result is bit for bit what it is without
+ *     this call.  A column with s_j == 0 next to shifted ones computes its unshifted values (fma(0, p, s) == s; only the sign of a
+ *     zero may differ);
+ *   - LAM_HIP_PC_JACOBI with shifts: M_j = diag(A) + s_j I, dinv_ij = 1 / ((double)A[i][i] + (double)s_j) rounded to the vector
+ *     dtype, one K-wide vector built and scanned by one launch per (matrix content, shifts).  The rule of the diagonal is on the
+ *     SUM: the first (row, column) whose sum or reciprocal is not finite and > 0 is refused as lam_hip_solve_many_pc refuses a
+ *     diagonal -- LAM_HIP_EINVAL naming row, column and value, nothing iterated, no batched solution afterwards -- and a zero on
+ *     A's own diagonal is fine where the shift lifts it;
+ *   - stats, gemv_bytes, the per-column arrays, frozen columns, NaN confinement, max_iters + 1 at the cap, the born-stopped
+ *     column at k = 0 and "multi_rhs_k" are unchanged.  No launch, no device traffic: the shifts travel in the kernel arguments. */
+int lam_hip_set_shifts_many(lam_hip_ctx *ctx, int nrhs, const double *sigma);
 /* The stored diagonal A[i][i], N elements of the vector dtype (LAM_HIP_BF16 storage: the stored bf16 values as float, exactly),
  * extracted on the device(s) from the pitched matrix.  Single-process contexts with any number of shards, every storage type;
  * rank mode: LAM_HIP_EINVAL; no matrix set: LAM_HIP_ESTATE.  No reference counterpart: the reference is un-preconditioned
