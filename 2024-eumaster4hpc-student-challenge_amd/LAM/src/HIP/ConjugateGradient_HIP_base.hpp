@@ -357,6 +357,34 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         _batch_failed = false;
         return true;
     }
+    // Multi-shift CG (lam_hip_solve_mshift): (A + sigma[j] I) x_j = b for ONE right-hand side b and 1..LAM_HIP_MAX_SHIFTS shifts, the
+    // single-column product of the smallest shift's system per iteration.  X (may be null): shift j's solution at X + j * cols.  The
+    // call replaces the batch's right-hand sides and shifts with the seed's (b, the smallest shift); the shifts kept by
+    // set_shifts_many are untouched and reach the library again with the next solve_many*'s right-hand sides.
+    // Returns true iff every shift converged; batch_failed() as for solve_many.  Members of their own for solve_many's reason:
+    // only programs that call them need an ABI that has the entry points.
+    bool solve_mshift(int nshifts, const double *sigma, const FloatingType *b, FloatingType *X, int max_iters, FloatingType rel_error,
+                      int32_t *num_iters = nullptr, int32_t *converged = nullptr, double *rel_err = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        lam_hip_stats st;
+        if (lam_hip_solve_mshift(_ctx, b, nshifts, sigma, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0)
+            return report("solve_mshift");
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_mshift(_ctx, nshifts, X) != 0) return report("get_solution_mshift");
+        _batch_failed = false;
+        return st.converged != 0;
+    }
+    // ||b - (A + sigma[j] I) x_j|| / ||b|| of the first nshifts shifts of the last solve_mshift, one K = 8 product per 8 shifts
+    bool true_residual_mshift(int nshifts, double *rel_res)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_true_residual_mshift(_ctx, nshifts, rel_res) != 0) return report("true_residual_mshift");
+        _batch_failed = false;
+        return true;
+    }
 
     // rows held by this process (all of them in the single-process classes), like the reference getters
     size_t get_num_rows() const

@@ -17,6 +17,7 @@ TUNING_LIB = os.path.join(_HERE, "liblam_hip_tuning.so")
 F64, F32, BF16 = 0, 1, 2
 ABI_VERSION = 4     # include/lam_hip.h LAM_HIP_ABI_VERSION
 MAX_RHS = 8         # include/lam_hip.h LAM_HIP_MAX_RHS
+MAX_SHIFTS = 64     # include/lam_hip.h LAM_HIP_MAX_SHIFTS
 PC_NONE, PC_JACOBI = 0, 1   # include/lam_hip.h LAM_HIP_PC_*: preconditioner of Solver.solve_many / solve_all
 _VEC_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
 _HOST_MAT_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
@@ -136,6 +137,10 @@ def lib():
             "lam_hip_get_solution_many": ([vp, i32, vp], i32),
             "lam_hip_gemv_many": ([vp, i32, vp, vp], i32),
             "lam_hip_gemv_many_only": ([vp, i32, i32, C.POINTER(C.c_double)], i32),
+            "lam_hip_solve_mshift": ([vp, vp, i32, C.POINTER(C.c_double), i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_double)], i32),
+            "lam_hip_get_solution_mshift": ([vp, i32, vp], i32),
+            "lam_hip_true_residual_mshift": ([vp, i32, C.POINTER(C.c_double)], i32),
             "lam_hip_check_symmetry": ([vp, C.POINTER(C.c_double)], i32),
             "lam_hip_debug_symv_plan": ([u64, i32, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)], i32),
             "lam_hip_dot": ([vp, vp, vp, u64, C.POINTER(C.c_double)], i32),
@@ -442,6 +447,42 @@ class Solver:
         self.set_rhs_many(np.repeat(b, sg.size, axis=0))
         self.set_shifts(sg)
         return self.solve_many(max_iters, rel_error, precond, x0)
+
+    def solve_multishift(self, b, shifts, max_iters, rel_error):
+        """(A + shifts[j] I) x_j = b for 1..MAX_SHIFTS shifts by multi-shift CG (lam_hip_solve_mshift): the single-column product of
+        the smallest shift's system per iteration, whatever the number of shifts.  Returns the per-shift `converged` array;
+        self.num_iters_shift / converged_shift / rel_err_shift hold the per-shift results and self.stats the call's.  The batch
+        state afterwards is the seed's: one right-hand side b under the smallest shift (solutions(), true_residuals())."""
+        sg = np.ascontiguousarray(np.atleast_1d(shifts), dtype=np.float64)
+        assert sg.ndim == 1, "shifts are a list of numbers"
+        b = np.ascontiguousarray(b, dtype=self.vec_dtype).reshape(-1)
+        assert b.size == self.n, "one right-hand side of N elements"
+        k = sg.size
+        ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        st = Stats()
+        self._chk(self._L.lam_hip_solve_mshift(self._h, b.ctypes.data_as(C.c_void_p), k, sg.ctypes.data_as(C.POINTER(C.c_double)),
+                                               max_iters, rel_error, C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               cv.ctypes.data_as(C.POINTER(C.c_int32)), re.ctypes.data_as(C.POINTER(C.c_double))))
+        self.nrhs = 1
+        self.nshifts = k
+        self.stats = st.asdict()
+        self.num_iters_shift, self.converged_shift, self.rel_err_shift = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
+        return self.converged_shift
+
+    def multishift_solutions(self):
+        """(nshifts, N): row j is the solution under shift j of the last solve_multishift."""
+        k = getattr(self, "nshifts", 0)
+        X = np.empty((max(k, 1), self.n), dtype=self.vec_dtype)
+        self._chk(self._L.lam_hip_get_solution_mshift(self._h, k, X.ctypes.data_as(C.c_void_p)))
+        return X[:k]
+
+    def multishift_true_residuals(self):
+        """||b - (A + s_j I) x_j|| / ||b|| of every shift of the last solve_multishift, formed on the device with one K = 8 product
+        per group of 8 shifts (lam_hip_true_residual_mshift).  The solutions and the seed's batch stay readable."""
+        k = getattr(self, "nshifts", 0)
+        r = np.zeros(max(k, 1), np.float64)
+        self._chk(self._L.lam_hip_true_residual_mshift(self._h, k, r.ctypes.data_as(C.POINTER(C.c_double))))
+        return r[:k].copy()
 
     def solve_many(self, max_iters, rel_error, precond=PC_NONE, x0=None):
         """Independent CG recurrences for the right-hand sides of set_rhs_many, one pass over the matrix per iteration.  Returns

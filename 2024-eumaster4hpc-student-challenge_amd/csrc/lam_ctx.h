@@ -87,6 +87,17 @@ struct ShardBase {
 // independent of it.  Allocated at the first batched call for LAM_HIP_MAX_RHS columns (5 vectors of 8 n elements: 21 MB at
 // n = 65536 in fp64, next to a 34 GB matrix), so it only ever grows with n; released by lam_hip_destroy and by a
 // lam_hip_set_problem that changes n.  All vectors are interleaved [n][K] (lam_kernels.h, "Several right-hand sides").
+// Multi-shift CG (lam_hip_solve_mshift): x and p of every shift in groups of 8, [n + 16][8] per group, and the per-shift scalars.
+// Allocated at the first multi-shift call for the groups it needs, grow-only, released with the batch (multi_release).
+struct MshiftState {
+    void *XS = nullptr, *PS = nullptr;
+    int groups_cap = 0;          // groups XS / PS hold
+    MshiftScalars *sc = nullptr; // device
+    int nshifts = 0;             // of the last solve
+    double shift[kMaxShifts] = {};    // absolute, each exactly a value of the vector dtype
+    bool valid = false;          // the multi-shift solution is readable: cleared by whatever clears or replaces the batch's
+};
+
 struct MultiState {
     uint64_t n = 0;              // the problem size the buffers were allocated for (0: none)
     void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
@@ -107,6 +118,7 @@ struct MultiState {
     // shifted == some shift[j] != 0, and only then do the SHIFT instantiations run.  Cleared with the right-hand sides.
     double shift[kMaxRhs] = {};
     bool shifted = false;
+    MshiftState ms;
 };
 
 // Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,
@@ -327,7 +339,7 @@ void matrix_changed(lam_hip_ctx *c)
     c->cg_ready = false;
     c->matrix_gen++;
     c->sym_refused = false;
-    c->multi.solved = false;
+    c->multi.solved = c->multi.ms.valid = false;
 }
 
 // ConjugateGradient_CPU_MPI_OMP.hpp:176-184: n/P rows each, the remainder on the LAST rank (lam_host_plan.h)

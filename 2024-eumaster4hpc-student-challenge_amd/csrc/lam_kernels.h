@@ -2936,6 +2936,186 @@ multi_deinterleave_kernel(const TV *__restrict__ inter, int ncols, TV *__restric
 
 
 // ---------------------------------------------------------------------------------------------
+// Multi-shift CG (lam_hip_solve_mshift, lam_multi.h): (A + s_j I) x_j = b for up to kMaxShifts shifts and ONE b.  The shifted Krylov
+// spaces are one space and the shifted residuals stay collinear with the seed's, r_j = zeta_j r (Jegerlehner; Frommer), so the
+// K = 1 batch on the smallest shift (the seed) is the only product, and one launch per iteration behind multi_p_kernel advances
+// every other shift from the seed's alpha, beta and r.  With d_j = s_j - s_min, a / b the seed's alpha / beta, Z_0 = Z_1 = 1,
+// a_0 = 1, b_0 = 0, iteration k = 1, 2, ...:
+//   Z_{k+1} = Z_k Z_{k-1} a_{k-1} / (a_k b_{k-1} (Z_{k-1} - Z_k) + Z_{k-1} a_{k-1} (1 + d_j a_k))
+//   x_j += (a_k Z_{k+1} / Z_k) p_j ;  rel_err_j = Z_{k+1} sqrt(rr_k / bb) ;  stop if rel_err_j < rel_error, else
+//   p_j = Z_{k+1} r + b_k (Z_{k+1} / Z_k)^2 p_j                          (r: the seed's R, already updated by multi_xr_kernel)
+// All scalars fp64; the three coefficients are rounded to the vector dtype once per shift and iteration.
+//
+// Layout: shifts live in groups of G = 8, XS and PS interleaved [n + kMultiPadRows][G] per group -- the K = 8 batch layout, so the
+// true residual hands a group to the K = 8 product as it is.  Slots past nshifts and slots with d_j == 0 (the seed's own shift: their
+// x is the batch's X, copied by mshift_copy_seed_kernel) are born frozen with x = p = 0.
+// Who decides: every workgroup recomputes Z_{k+1} and the coefficients from slots nobody writes in this launch (the zeta ring's
+// slots k % 3 and (k - 1) % 3, the seed ring's slot (k - 1) & 1); workgroup (0, g) alone writes the new ones.  frozen_at is the
+// first iteration in which the shift does nothing: a stop at k still takes iteration k's x update, so it writes k + 1, and a
+// workgroup that starts later reads "live at k", which is what it would have decided itself from the same bits (multi_p_kernel's
+// argument); an underflow at k writes k, and the late workgroup reads what it would have found.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMaxShifts = 64;
+constexpr int kShiftGroup = 8;
+struct MshiftScalars {
+    double zeta[kMaxShifts][3];   // Z_m at [m % 3]
+    double d[kMaxShifts];         // s_j - s_min >= 0
+    double rel_err[kMaxShifts];   // of the last completed step
+    double seed_ab[2][2];         // the seed's {alpha, beta} of iteration k at [k & 1]
+    int frozen_at[kMaxShifts];    // 0: live; else the first iteration in which the shift does nothing
+    int iters[kMaxShifts];        // last completed step
+    int stop[kMaxShifts];         // met its stop test
+};
+struct MshiftList { double d[kMaxShifts]; };
+
+// x = 0, p = b for the live slots (0 for the others) of every group, and the scalars' start values; grid (vec_grid(n), groups)
+template <typename TV, int G>
+__global__ void __launch_bounds__(kBlock)
+mshift_init_kernel(const TV *__restrict__ B, TV *__restrict__ XS, TV *__restrict__ PS, uint64_t n, int nshifts, MshiftList dl,
+                   MshiftScalars *ms)
+{
+    const int g = blockIdx.y;
+    const uint64_t base = (uint64_t)g * (n + kMultiPadRows) * G;
+    bool live[G];
+#pragma unroll
+    for (int j = 0; j < G; j++) live[j] = g * G + j < nshifts && dl.d[g * G + j] > 0.0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const TV bi = B[i];
+#pragma unroll
+        for (int j = 0; j < G; j++) {
+            XS[base + i * G + j] = (TV)0;
+            PS[base + i * G + j] = live[j] ? bi : (TV)0;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < G) {
+        const int slot = g * G + threadIdx.x;
+        const bool lv = slot < nshifts && dl.d[slot] > 0.0;
+        ms->zeta[slot][0] = ms->zeta[slot][1] = ms->zeta[slot][2] = 1.0;
+        ms->d[slot] = slot < nshifts ? dl.d[slot] : 0.0;
+        ms->rel_err[slot] = 1.0;
+        ms->frozen_at[slot] = lv ? 0 : 1;
+        ms->iters[slot] = 0;
+        ms->stop[slot] = 0;
+        if (slot == 0) {
+            ms->seed_ab[0][0] = 1.0; ms->seed_ab[0][1] = 0.0;
+            ms->seed_ab[1][0] = 0.0; ms->seed_ab[1][1] = 0.0;
+        }
+    }
+}
+
+// iteration k of every live shift, behind multi_p_kernel of iteration k; grid (vec_grid(n), groups).  The launches the lag rule
+// enqueues past the seed's stop find seed.iters != k and return at once, before they read scalars that belong to another
+// iteration.  Results cannot show this guard: a shift that has stopped is frozen by frozen_at anyway, and a shift still live
+// behind the seed's stop needs zeta > 1, which only rounding could produce (mutations).
+template <typename TV, int G>
+__global__ void __launch_bounds__(kBlock)
+mshift_step_kernel(const MultiScalars *sc, MshiftScalars *ms, int k, double rel_error, const TV *__restrict__ R, TV *__restrict__ XS,
+                   TV *__restrict__ PS, uint64_t n)
+{
+    const CgScalars &seed = sc->col[0];
+    if (seed.iters != k) return;
+    const int g = blockIdx.y;
+    const double a = seed.alpha, b = seed.beta, rel = sqrt(seed.rr[k & 1] / seed.bb);
+    const double a_prev = ms->seed_ab[(k - 1) & 1][0], b_prev = ms->seed_ab[(k - 1) & 1][1];
+    bool live[G], cont[G];
+    TV cx[G], cr[G], cp[G];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < G; j++) {
+        const int slot = g * G + j;
+        const int fz = ms->frozen_at[slot];
+        const bool was_live = fz == 0 || k < fz;
+        const double z0 = ms->zeta[slot][k % 3], zm = ms->zeta[slot][(k + 2) % 3], d = ms->d[slot];
+        const double z1 = z0 * zm * a_prev / (a * b_prev * (zm - z0) + zm * a_prev * (1.0 + d * a));
+        // finite, but zero or subnormal: the shift has converged past what fp64 can scale r by and is frozen BEFORE this step
+        // (a NaN is not: it runs to the cap as a batch column's would)
+        const bool under = fabs(z1) < std::numeric_limits<double>::min();
+        const double ratio = z1 / z0, re = z1 * rel;
+        const bool stop = re < rel_error;
+        live[j] = was_live && !under;
+        cont[j] = live[j] && !stop;
+        cx[j] = (TV)(a * ratio);
+        cr[j] = (TV)z1;
+        cp[j] = (TV)(b * ratio * ratio);
+        any = any || live[j];
+        if (was_live && blockIdx.x == 0 && threadIdx.x == 0) {
+            if (under) {
+                ms->frozen_at[slot] = k;
+            } else {
+                ms->zeta[slot][(k + 1) % 3] = z1;
+                ms->rel_err[slot] = re;
+                ms->iters[slot] = k;
+                if (stop) { ms->stop[slot] = 1; ms->frozen_at[slot] = k + 1; }
+            }
+        }
+    }
+    if (g == 0 && blockIdx.x == 0 && threadIdx.x == 0) { ms->seed_ab[k & 1][0] = a; ms->seed_ab[k & 1][1] = b; }
+    if (!any) return;
+    const uint64_t base = (uint64_t)g * (n + kMultiPadRows) * G;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const TV ri = R[i];
+#pragma unroll
+        for (int j = 0; j < G; j++) {
+            if (!live[j]) continue;
+            const uint64_t e = base + i * G + j;
+            const TV pi = PS[e];
+            XS[e] = cx[j] * pi + XS[e];
+            if (cont[j]) PS[e] = fma_tv(cr[j], ri, cp[j] * pi);
+        }
+    }
+}
+
+// the slots of `mask` (bit = slot) hold the seed's own shift: their x is the batch's X (K = 1 layout), copied, not recomputed
+template <typename TV, int G>
+__global__ void __launch_bounds__(kBlock)
+mshift_copy_seed_kernel(const TV *__restrict__ X, TV *__restrict__ XS, uint64_t n, unsigned long long mask)
+{
+    const int g = blockIdx.y;
+    const unsigned gm = (unsigned)(mask >> (g * G)) & ((1u << G) - 1u);
+    if (gm == 0) return;
+    const uint64_t base = (uint64_t)g * (n + kMultiPadRows) * G;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const TV xi = X[i];
+#pragma unroll
+        for (int j = 0; j < G; j++)
+            if (gm >> j & 1u) XS[base + i * G + j] = xi;
+    }
+}
+
+// lam_hip_true_residual_mshift: multi_residual_kernel against the ONE b: with Y = (A + s_j I) x_j of a group from the K = 8
+// product, r = b - y_j rounded to the vector dtype; fp64 partials of r_j.r_j and (the same for every j) of b.b, laid out for
+// multi_residual_scalars_kernel
+template <typename TV, int G>
+__global__ void __launch_bounds__(kBlock)
+mshift_residual_kernel(const TV *__restrict__ B, const TV *__restrict__ Y, uint64_t n, double *__restrict__ partial_rr,
+                       double *__restrict__ partial_bb)
+{
+    __shared__ double s_red[kWaves];
+    double acc[G], accb = 0.0;
+#pragma unroll
+    for (int j = 0; j < G; j++) acc[j] = 0.0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        const TV bi = B[i];
+        accb += (double)bi * (double)bi;
+#pragma unroll
+        for (int j = 0; j < G; j++) {
+            const TV ri = bi - Y[i * G + j];
+            acc[j] += (double)ri * (double)ri;
+        }
+    }
+    const double tb = block_sum(accb, s_red);
+#pragma unroll
+    for (int j = 0; j < G; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) {
+            partial_rr[(size_t)j * gridDim.x + blockIdx.x] = t;
+            partial_bb[(size_t)j * gridDim.x + blockIdx.x] = tb;
+        }
+    }
+}
+
+
+// ---------------------------------------------------------------------------------------------
 // The diagonal of the matrix: lam_hip_get_diagonal, and dinv of the preconditioned batch (PC above).
 // ---------------------------------------------------------------------------------------------
 // what the extraction found wrong with the diagonal: rows whose A_ii or 1/A_ii is not finite and > 0

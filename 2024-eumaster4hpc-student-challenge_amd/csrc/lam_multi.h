@@ -18,6 +18,8 @@
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
+static_assert(lam::kMaxShifts == LAM_HIP_MAX_SHIFTS, "include/lam_hip.h states the limit");
+static_assert(lam::kShiftGroup == lam::kMaxRhs, "a group of shifts is handed to the K = 8 product as it is");
 
 namespace {
 
@@ -44,6 +46,7 @@ void multi_release(lam_hip_ctx *c)
     free_dev({c->pcg.diag, c->pcg.dinv, c->pcg.dinv_k, c->pcg.part_rz, c->pcg.info});
     c->pcg = PcgState();
     free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.part_rr, m.res, m.sc});
+    free_dev({m.ms.XS, m.ms.PS, m.ms.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -335,7 +338,7 @@ int lam_hip_set_rhs_many(lam_hip_ctx *c, int nrhs, const void *b_host)
     if (!c->have_problem) return fail(c, LAM_HIP_ESTATE, "call lam_hip_set_problem first");
     LAMCHK(multi_ensure(c));
     MultiState &m = c->multi;
-    m.have_rhs = m.solved = false;
+    m.have_rhs = m.solved = m.ms.valid = false;
     multi_clear_shifts(m);
     const int K = multi_k_for(nrhs);
     LAMCHK(multi_upload(c, nrhs, K, b_host, m.B));
@@ -385,8 +388,10 @@ enum MultiGuess { kGuessNone, kGuessHost, kGuessCurrent };
 // per-column results are shared.  A start from a guess stages the guess in P (whose rows behind row n the product needs zero; the
 // upload and multi_stage_solution see to that), forms A x0 in AP with one more product launch and runs the GUESS = true
 // instantiations of the two init kernels; the loop is the same loop.
+// mshift (lam_hip_solve_mshift only, null for every other entry point): the multi-shift state the K = 1 seed batch drives -- one init
+// launch in front of the loop and one step launch behind every multi_p_kernel; nothing else changes, the seed's progress word decides.
 int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, const void *x0_host, int max_iters, double rel_error,
-                lam_hip_stats *st, int32_t *num_iters, int32_t *converged, double *rel_err)
+                lam_hip_stats *st, int32_t *num_iters, int32_t *converged, double *rel_err, MshiftState *mshift = nullptr)
 {
     LAMCHK(multi_supported(c, fn));
     if (precond != LAM_HIP_PC_NONE && precond != LAM_HIP_PC_JACOBI)
@@ -404,6 +409,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     PcgState &g = c->pcg;
     m.solved = false;            // whatever follows, a refusal of the diagonal included, leaves no batched solution behind
+    m.ms.valid = false;          // and the batch's vectors are no longer the seed's of a multi-shift solve
     const bool dk = pc && m.shifted;             // M_j = diag(A) + s_j I: the K-wide reciprocal
     const double *const shift = m.shifted ? m.shift : nullptr;
     if (dk) {
@@ -453,6 +459,14 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
         hipLaunchKernelGGL((multi_init_scalars_kernel<K, PC, GUESS>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb,
                            m.nrhs, m.sc, (volatile int *)m.host_flags, (const double *)part_rz, (const double *)part_rr, rel_error);
         HIPCHK(c, hipGetLastError());
+        const int sgroups = mshift ? (mshift->nshifts + kShiftGroup - 1) / kShiftGroup : 0;
+        if (mshift) {
+            MshiftList dl;
+            for (int j = 0; j < kMaxShifts; j++) dl.d[j] = j < mshift->nshifts ? mshift->shift[j] - m.shift[0] : 0.0;
+            hipLaunchKernelGGL((mshift_init_kernel<TV, kShiftGroup>), dim3(vb, sgroups), dim3(kBlock), 0, s0.stream, (const TV *)m.B,
+                               (TV *)mshift->XS, (TV *)mshift->PS, c->n, mshift->nshifts, dl, mshift->sc);
+            HIPCHK(c, hipGetLastError());
+        }
         for (int i = 0; i < max_iters; i++) {
             const int k = i + 1, slot = i % kLag;
             if (i >= kLag) {
@@ -473,6 +487,12 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
             hipLaunchKernelGGL((multi_p_kernel<TV, K, PC, DK>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.sc, k,
                                rel_error, (const TV *)m.R, (TV *)m.P, c->n, (volatile int *)m.host_flags, dinv, (const double *)part_rz);
             LAUNCHED(c);
+            if (mshift) {
+                hipLaunchKernelGGL((mshift_step_kernel<TV, kShiftGroup>), dim3(vb, sgroups), dim3(kBlock), 0, s0.stream,
+                                   (const MultiScalars *)m.sc, mshift->sc, k, rel_error, (const TV *)m.R, (TV *)mshift->XS,
+                                   (TV *)mshift->PS, c->n);
+                LAUNCHED(c);
+            }
             c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
             enq++;
         }
@@ -627,7 +647,7 @@ int lam_hip_gemv_many(lam_hip_ctx *c, int nrhs, const void *x_host, void *y_host
     LAMCHK(multi_ensure(c));
     MultiState &m = c->multi;
     LAMCHK(set_dev(c, c->sh[0]));
-    m.solved = false;            // P and AP of the batch are overwritten (B is not: a following lam_hip_solve_many starts from it)
+    m.solved = m.ms.valid = false;      // P and AP of the batch are overwritten (B is not: a following lam_hip_solve_many starts from it)
     const int K = multi_k_for(nrhs);
     m.last_K = K;
     LAMCHK(multi_upload(c, nrhs, K, x_host, m.P));
@@ -650,7 +670,7 @@ int lam_hip_gemv_many_only(lam_hip_ctx *c, int nrhs, int reps, double *sec_per_p
     MultiState &m = c->multi;
     ShardBase &s = c->sh[0];
     LAMCHK(set_dev(c, s));
-    m.solved = false;
+    m.solved = m.ms.valid = false;
     const int K = multi_k_for(nrhs);
     m.last_K = K;
     LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
@@ -671,6 +691,208 @@ int lam_hip_gemv_many_only(lam_hip_ctx *c, int nrhs, int reps, double *sec_per_p
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, m.ev0[0], m.ev1[0]));
     *sec_per_product = (double)ms * 1e-3 / reps;
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+int mshift_check_n(lam_hip_ctx *c, const char *fn, int nshifts)
+{
+    if (nshifts < 1 || nshifts > LAM_HIP_MAX_SHIFTS)
+        return fail(c, LAM_HIP_EINVAL, "%s: nshifts = %d, must be 1..%d (LAM_HIP_MAX_SHIFTS)", fn, nshifts, LAM_HIP_MAX_SHIFTS);
+    return 0;
+}
+
+// XS / PS for `groups` groups of the batch's n (multi_ensure has run): grow-only; zero once, so that the rows behind row n stay zero
+int mshift_ensure(lam_hip_ctx *c, int groups)
+{
+    MshiftState &ms = c->multi.ms;
+    if (!ms.sc) HIPCHK(c, hipMalloc((void **)&ms.sc, sizeof(MshiftScalars)));
+    if (groups <= ms.groups_cap) return 0;
+    ShardBase &s = c->sh[0];
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    free_dev({ms.XS, ms.PS});
+    ms.XS = ms.PS = nullptr;
+    ms.groups_cap = 0;
+    const size_t bytes = (size_t)groups * (c->n + kMultiPadRows) * kShiftGroup * c->esz_v();
+    HIPCHK(c, hipMalloc(&ms.XS, bytes));
+    HIPCHK(c, hipMalloc(&ms.PS, bytes));
+    HIPCHK(c, hipMemsetAsync(ms.XS, 0, bytes, s.stream));
+    HIPCHK(c, hipMemsetAsync(ms.PS, 0, bytes, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    ms.groups_cap = groups;
+    return 0;
+}
+
+// f(Impl<TA, TV>()) for the context's dtype: the multi-shift kernels have the one group width
+template <typename F>
+int mshift_dispatch(lam_hip_ctx *c, F &&f)
+{
+    if (c->dtype == LAM_HIP_F64) return f(Impl<double, double>());
+    if (c->dtype == LAM_HIP_F32) return f(Impl<float, float>());
+    return fail(c, LAM_HIP_EINVAL, "the multi-shift path has no kernels for dtype %d", c->dtype);
+}
+
+int mshift_readable(lam_hip_ctx *c, const char *fn, int nshifts)
+{
+    MultiState &m = c->multi;
+    if (!m.solved || !m.ms.valid || m.n != c->n) return fail(c, LAM_HIP_ESTATE, "no multi-shift solution yet (lam_hip_solve_mshift)");
+    if (nshifts > m.ms.nshifts) return fail(c, LAM_HIP_EINVAL, "%s: %d shifts asked, %d were solved", fn, nshifts, m.ms.nshifts);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The seed is the K = 1 batch on the smallest shift: lam_hip_set_rhs_many(1, b) + lam_hip_set_shifts_many(1, &s_min) +
+// lam_hip_solve_many with the multi-shift hook, so the batch state afterwards is the seed's.
+int lam_hip_solve_mshift(lam_hip_ctx *c, const void *b_host, int nshifts, const double *sigma, int max_iters, double rel_error,
+                         lam_hip_stats *st, int32_t *num_iters, int32_t *converged, double *rel_err)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    const char *const fn = "lam_hip_solve_mshift";
+    LAMCHK(multi_supported(c, fn));
+    LAMCHK(mshift_check_n(c, fn, nshifts));
+    if (!b_host || !sigma) return fail(c, LAM_HIP_EINVAL, "%s: b_host or sigma is NULL", fn);
+    double sh[kMaxShifts] = {};
+    double s_min = 0.0;
+    for (int j = 0; j < nshifts; j++) {
+        const double r = c->dtype == LAM_HIP_F32 ? (double)(float)sigma[j] : sigma[j];
+        if (!(sigma[j] >= 0.0) || !std::isfinite(r))
+            return fail(c, LAM_HIP_EINVAL, "%s: shift %d is %g: every shift must be finite and >= 0, in the vector dtype too", fn, j,
+                        sigma[j]);
+        sh[j] = r;
+        s_min = j == 0 ? r : std::min(s_min, r);
+    }
+    if (!c->have_problem) return fail(c, LAM_HIP_ESTATE, "call lam_hip_set_problem first");
+    if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
+    LAMCHK(set_dev(c, c->sh[0]));
+    LAMCHK(multi_ensure(c));
+    MultiState &m = c->multi;
+    MshiftState &ms = m.ms;
+    m.have_rhs = m.solved = ms.valid = false;
+    multi_clear_shifts(m);
+    LAMCHK(mshift_ensure(c, (nshifts + kShiftGroup - 1) / kShiftGroup));
+    LAMCHK(multi_upload(c, 1, 1, b_host, m.B));
+    HIPCHK(c, hipStreamSynchronize(c->sh[0].stream));
+    m.nrhs = 1; m.K = 1;
+    m.have_rhs = true;
+    m.shift[0] = s_min;
+    m.shifted = s_min != 0.0;
+    ms.nshifts = nshifts;
+    memcpy(ms.shift, sh, sizeof sh);
+    lam_hip_stats seed_st;
+    int32_t seed_ni = 0, seed_cv = 0;
+    double seed_re = 0.0;
+    LAMCHK(multi_solve(c, fn, LAM_HIP_PC_NONE, kGuessNone, nullptr, max_iters, rel_error, &seed_st, &seed_ni, &seed_cv, &seed_re, &ms));
+    const double t0 = now_s();
+    ShardBase &s = c->sh[0];
+    unsigned long long seed_slots = 0;
+    for (int j = 0; j < nshifts; j++)
+        if (sh[j] == s_min) seed_slots |= 1ull << j;
+    const int groups = (nshifts + kShiftGroup - 1) / kShiftGroup;
+    LAMCHK(mshift_dispatch(c, [&](auto impl) -> int {
+        using TV = typename ImplTraits<decltype(impl)>::TV;
+        hipLaunchKernelGGL((mshift_copy_seed_kernel<TV, kShiftGroup>), dim3(vec_grid(c->n), groups), dim3(kBlock), 0, s.stream,
+                           (const TV *)m.X, (TV *)ms.XS, c->n, seed_slots);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }));
+    const std::unique_ptr<MshiftScalars> h(new MshiftScalars);
+    HIPCHK(c, hipMemcpyAsync(h.get(), ms.sc, sizeof(MshiftScalars), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    int most = 0, all_conv = 1;
+    double worst = 0.0;
+    bool any_nan = false;
+    for (int j = 0; j < nshifts; j++) {
+        int ni = seed_ni, cv = seed_cv;
+        double re = seed_re;
+        if (!(seed_slots >> j & 1ull)) {
+            // stopped: its iteration; frozen on an underflow of zeta: the last completed step, not converged; still live: the batch's
+            // convention for a column that never met its test (max_iters + 1 at the cap)
+            cv = h->stop[j] != 0;
+            ni = cv || h->frozen_at[j] != 0 ? h->iters[j] : h->iters[j] + 1;
+            re = h->iters[j] == 0 ? seed_re : h->rel_err[j];      // no step completed: the start's own sqrt(rr0 / bb), the seed's
+        }
+        if (num_iters) num_iters[j] = ni;
+        if (converged) converged[j] = cv;
+        if (rel_err) rel_err[j] = re;
+        most = std::max(most, ni);
+        all_conv = all_conv && cv;
+        if (re != re) any_nan = true; else worst = std::max(worst, re);
+    }
+    if (st) {
+        *st = seed_st;
+        st->num_iters = most;
+        st->converged = all_conv;
+        st->rel_err = any_nan ? std::nan("") : worst;
+        st->t_total += now_s() - t0;
+    }
+    ms.valid = true;
+    return 0;
+}
+
+int lam_hip_get_solution_mshift(lam_hip_ctx *c, int nshifts, void *x_host)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    const char *const fn = "lam_hip_get_solution_mshift";
+    LAMCHK(multi_supported(c, fn));
+    LAMCHK(mshift_check_n(c, fn, nshifts));
+    if (!x_host) return fail(c, LAM_HIP_EINVAL, "%s: x_host is NULL", fn);
+    LAMCHK(mshift_readable(c, fn, nshifts));
+    LAMCHK(set_dev(c, c->sh[0]));
+    const size_t ev = c->esz_v(), group_elems = (size_t)(c->n + kMultiPadRows) * kShiftGroup;
+    for (int first = 0; first < nshifts; first += kShiftGroup)
+        LAMCHK(multi_download(c, std::min(kShiftGroup, nshifts - first), kShiftGroup,
+                              (const char *)c->multi.ms.XS + (size_t)(first / kShiftGroup) * group_elems * ev,
+                              (char *)x_host + (size_t)first * c->n * ev));
+    return 0;
+}
+
+// Per group of 8 shifts: the group's X is [n][8], the K = 8 layout, so it is staged in P as a batch's X is and meets ONE K = 8
+// SHIFT = true product with the group's absolute shifts; then one pass b - Y against the single b.  P, AP, the partials and res are
+// scratch, as they are between any two solves; B, X and XS are left alone.
+int lam_hip_true_residual_mshift(lam_hip_ctx *c, int nshifts, double *rel_res)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    const char *const fn = "lam_hip_true_residual_mshift";
+    LAMCHK(multi_supported(c, fn));
+    LAMCHK(mshift_check_n(c, fn, nshifts));
+    if (!rel_res) return fail(c, LAM_HIP_EINVAL, "%s: rel_res is NULL", fn);
+    LAMCHK(mshift_readable(c, fn, nshifts));
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    LAMCHK(set_dev(c, s));
+    const int vb = vec_grid(c->n);
+    const size_t ev = c->esz_v(), body = (size_t)c->n * kShiftGroup * ev, group_bytes = (size_t)(c->n + kMultiPadRows) * kShiftGroup * ev;
+    for (int first = 0; first < nshifts; first += kShiftGroup) {
+        HIPCHK(c, hipMemcpyAsync(m.P, (const char *)m.ms.XS + (size_t)(first / kShiftGroup) * group_bytes, body, hipMemcpyDeviceToDevice,
+                                 s.stream));
+        HIPCHK(c, hipMemsetAsync((char *)m.P + body, 0, (size_t)kMultiPadRows * kShiftGroup * ev, s.stream));
+        double gs[kMaxRhs] = {};
+        for (int j = 0; j < kShiftGroup && first + j < nshifts; j++) gs[j] = m.ms.shift[first + j];
+        LAMCHK(mshift_dispatch(c, [&](auto impl) -> int {
+            using I = decltype(impl);
+            using TA = typename ImplTraits<I>::TA;
+            using TV = typename ImplTraits<I>::TV;
+            constexpr int K = kShiftGroup;
+            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr, gs)));
+            hipLaunchKernelGGL((mshift_residual_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s.stream, (const TV *)m.B, (const TV *)m.AP, c->n,
+                               m.part_rr, m.part_vec);
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL((multi_residual_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s.stream, (const double *)m.part_rr,
+                               (const double *)m.part_vec, vb, m.res);
+            HIPCHK(c, hipGetLastError());
+            return 0;
+        }));
+        double res[kMaxRhs];
+        HIPCHK(c, hipMemcpyAsync(res, m.res, sizeof res, hipMemcpyDeviceToHost, s.stream));
+        HIPCHK(c, hipStreamSynchronize(s.stream));
+        for (int j = 0; j < kShiftGroup && first + j < nshifts; j++) rel_res[first + j] = res[j];
+    }
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
-//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
@@ -9,6 +9,9 @@
 // -S s0,s1,...: 1 to 8 shifts >= 0 (lam_hip_set_shifts_many); they set nrhs, column j is (A + s_j I) x_j = b_j with the SAME
 // right-hand side in every column (constant 1), and the shift is one more CSV column at the end of the line.  With -J the
 // preconditioner is diag(A) + s_j I; with -w the second stage continues under the same shifts; -T measures against them.
+// -M (with -S, which may then list up to 64 shifts): multi-shift CG (lam_hip_solve_mshift) -- ONE right-hand side, column 0's
+// constant 1, and every shift solved behind the single-column product of the smallest shift's system; one CSV line per shift in the
+// same columns, -T prints lam_hip_true_residual_mshift's values.  -M without -S, with -J or with -w is refused.
 // Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
@@ -77,7 +80,39 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
     return 0;
 }
 
-// "s0,s1,...": 1..LAM_HIP_MAX_RHS numbers, each finite and >= 0, nothing else in the list
+// -M: every shift of -S against the one right-hand side b = 1 by multi-shift CG
+template <typename T>
+static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_res, const std::vector<double> &shifts)
+{
+    using clk = std::chrono::high_resolution_clock;
+    const int ns = (int)shifts.size();
+    LAM::ConjugateGradient_HIP<T> cg(0);
+    cg.set_text_output(false);
+    const auto t0 = clk::now();
+    if (!cg.generate_matrix(rows, rows)) {
+        fprintf(stderr, "Failed to generate matrix\n");
+        return 1;
+    }
+    const double t_load = std::chrono::duration<double>(clk::now() - t0).count();
+    const std::vector<T> b(rows, (T)1);
+    std::vector<int32_t> iters(ns), conv(ns);
+    std::vector<double> rel(ns), tres(ns);
+    const auto t1 = clk::now();
+    cg.solve_mshift(ns, shifts.data(), b.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data());
+    if (cg.batch_failed()) return 3;
+    const double t_cg = std::chrono::duration<double>(clk::now() - t1).count();
+    if (true_res && !cg.true_residual_mshift(ns, tres.data())) return 3;
+    const lam_hip_stats &st = cg.stats();
+    for (int j = 0; j < ns; j++) {
+        std::cout << rows << "," << 1 << "," << 1 << "," << t_load << "," << st.t_comm_init << "," << st.t_gemv << "," << st.t_iter << ","
+                  << iters[j] << "," << rel[j] << "," << t_cg;
+        if (true_res) std::cout << "," << tres[j];
+        std::cout << "," << shifts[j] << std::endl;
+    }
+    return 0;
+}
+
+// "s0,s1,...": 1..LAM_HIP_MAX_SHIFTS numbers (main holds a list without -M to LAM_HIP_MAX_RHS), each finite and >= 0, nothing else
 static bool parse_shifts(const char *arg, std::vector<double> *out)
 {
     out->clear();
@@ -85,7 +120,7 @@ static bool parse_shifts(const char *arg, std::vector<double> *out)
     for (;;) {
         char *end = nullptr;
         const double v = strtod(p, &end);
-        if (end == p || !(v >= 0.0) || !std::isfinite(v) || out->size() == (size_t)LAM_HIP_MAX_RHS) return false;
+        if (end == p || !(v >= 0.0) || !std::isfinite(v) || out->size() == (size_t)LAM_HIP_MAX_SHIFTS) return false;
         out->push_back(v);
         if (*end == '\0') return true;
         if (*end != ',') return false;
@@ -99,11 +134,11 @@ int main(int argc, char **argv)
     int nrhs = 1, max_iters = 1000, opt;
     double rel_error = 1e-9;
     const char *precision = "f64";
-    bool jacobi = false, true_res = false;
+    bool jacobi = false, true_res = false, mshift = false;
     int warm = -1;                  // -1: no -w
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:h")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:Mh")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
@@ -114,15 +149,33 @@ int main(int argc, char **argv)
         case 'w': warm = atoi(optarg); bad_warm = warm < 0; break;
         case 'T': true_res = true; break;
         case 'S': bad_shifts = !parse_shifts(optarg, &shifts); break;
+        case 'M': mshift = true; break;
         default:
             fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
-                    "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)]\n", argv[0],
-                    LAM_HIP_MAX_RHS);
+                    "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)] "
+                    "[-M (with -S, up to %d shifts: multi-shift CG on one right-hand side; not with -J, -w)]\n", argv[0],
+                    LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS);
             return opt == 'h' ? 0 : 1;
         }
     }
+    if (mshift && (shifts.empty() || bad_shifts || jacobi || warm >= 0 || bad_warm || k_given)) {
+        fprintf(stderr, "Usage: -M needs -S s0,s1,... (1..%d finite shifts >= 0) and takes neither -J, -w nor -k: multi-shift CG has one "
+                "right-hand side, no preconditioner and no guess\n", LAM_HIP_MAX_SHIFTS);
+        return 1;
+    }
+    if (!mshift && shifts.size() > (size_t)LAM_HIP_MAX_RHS) bad_shifts = true;
     if (bad_shifts || (!shifts.empty() && k_given && nrhs != (int)shifts.size())) {
         fprintf(stderr, "-S takes 1..%d comma-separated finite shifts >= 0, and -k, if given, their number\n", LAM_HIP_MAX_RHS);
+        return 1;
+    }
+    if (mshift) {
+        if (rows == 0 || max_iters < 0) {
+            fprintf(stderr, "Usage: %s -s N -i max_iters [-e rel_error] [-t f64|f32] [-T] -S s0,s1,... -M\n", argv[0]);
+            return 1;
+        }
+        if (!strcmp(precision, "f64")) return run_mshift<double>(rows, max_iters, rel_error, true_res, shifts);
+        if (!strcmp(precision, "f32")) return run_mshift<float>(rows, max_iters, rel_error, true_res, shifts);
+        fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
         return 1;
     }
     if (!shifts.empty()) nrhs = (int)shifts.size();

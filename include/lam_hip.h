@@ -50,7 +50,9 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): LAM_HIP_PC_NONE, LAM_HIP_PC_JACOBI, lam_hip_solve_many_pc and
  *      lam_hip_get_diagonal.
  *      Added under version 4 likewise (purely additive): lam_hip_solve_many_x0 and lam_hip_true_residual_many.
- *      Added under version 4 likewise (purely additive): lam_hip_set_shifts_many. */
+ *      Added under version 4 likewise (purely additive): lam_hip_set_shifts_many.
+ *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_SHIFTS, lam_hip_solve_mshift, lam_hip_get_solution_mshift and
+ *      lam_hip_true_residual_mshift. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -335,6 +337,51 @@ int lam_hip_gemv_many(lam_hip_ctx *ctx, int nrhs, const void *x_host, void *y_ho
 /* `reps` back-to-back launches of the batched product kernel for nrhs columns, timed with HIP events; *sec_per_product =
  * average seconds per launch.  The counterpart of lam_hip_gemv_only. */
 int lam_hip_gemv_many_only(lam_hip_ctx *ctx, int nrhs, int reps, double *sec_per_product);
+
+/* ---- multi-shift CG: every shift of (A + s_j I) x_j = b for one pass over A ---------------------
+ * ONE right-hand side, 1..LAM_HIP_MAX_SHIFTS shifts -- the ridge / Tikhonov sweep or noise-level scan lam_hip_set_shifts_many names
+ * first, without replicating b and without the K = 8 product.  For a common b and x0 = 0 the shifted Krylov spaces are one space
+ * and the shifted residuals stay collinear with the seed's, r_j = zeta_j r (Jegerlehner; Frommer), so per iteration there is the
+ * single-column product of the seed system and one fused vector launch for all shifts.  No reference counterpart.
+ *   - b_host: N elements of the vector dtype.  nshifts outside 1..LAM_HIP_MAX_SHIFTS: LAM_HIP_EINVAL.  Every sigma[j] must be finite
+ *     and >= 0, and finite after rounding to the vector dtype (lam_hip_set_shifts_many's rule): anything else is LAM_HIP_EINVAL and
+ *     the message names the column and the value.  Supports what the batch supports: several shards, rank mode and LAM_HIP_BF16 are
+ *     refused with the same codes and words; no matrix set: LAM_HIP_ESTATE.  No preconditioner and no initial guess: neither
+ *     composes with the collinearity (use lam_hip_set_shifts_many for those);
+ *   - the SEED is the smallest shift after rounding, s_min, and d_j = (double)s_j - (double)s_min >= 0.  The seed run is the K = 1
+ *     batch: lam_hip_set_rhs_many(1, b) + lam_hip_set_shifts_many(1, &s_min) + lam_hip_solve_many, the same launches plus one per
+ *     iteration.  The call therefore REPLACES the batch's right-hand sides and shifts, and afterwards the batch state is the
+ *     seed's: lam_hip_get_solution_many(1), lam_hip_true_residual_many(1) and lam_hip_solve_many_x0(..., NULL, ...) work on it.
+ *     Every j with d_j == 0 reports the seed's x, num_iters, converged and rel_err bit for bit (copied from the batch's X, not
+ *     recomputed); s_min == 0 runs the unshifted product;
+ *   - the recurrence, per shift j with d_j > 0, a_k / beta_k / rr_k the seed's alpha, beta and r.r of iteration k = 0, 1, ...,
+ *     zeta_{-1} = zeta_0 = 1, a_{-1} = 1, beta_{-1} = 0, x_j = 0, p_j = b, behind the seed's x, r and p update of iteration k:
+ *         zeta_{k+1} = zeta_k zeta_{k-1} a_{k-1} / (a_k beta_{k-1} (zeta_{k-1} - zeta_k) + zeta_{k-1} a_{k-1} (1 + d_j a_k))
+ *         x_j += (a_k zeta_{k+1} / zeta_k) p_j ;  rel_err_j = zeta_{k+1} sqrt(rr_k / bb)
+ *         if rel_err_j < rel_error: shift j stops, FROZEN like a batch column, num_iters_j = the iteration (counted from 1)
+ *         else p_j = zeta_{k+1} r + beta_k (zeta_{k+1} / zeta_k)^2 p_j                     (r: the seed's, already updated)
+ *     all scalars fp64, the three coefficients rounded to the vector dtype once per shift and iteration.  The loop ends when the
+ *     seed stops or at the cap: a shift still live when the seed stops gets that iteration's x update and its own test (in exact
+ *     arithmetic zeta <= 1, so it passes); at the cap an unconverged shift reports max_iters + 1, the batch's convention;
+ *   - max_iters = 0 is legal and completes no step: every x_j = 0, converged = 0, num_iters = max_iters + 1 = 1 and rel_err = the
+ *     start's sqrt(bb/bb) = 1 (NaN for b = 0) for every shift, the seed's slots included, as lam_hip_solve_many reports it;
+ *   - if zeta_{k+1} is finite but zero or subnormal the shift is frozen BEFORE that step and reports converged = 0, num_iters = the
+ *     last completed step and that step's rel_err: its residual is below what fp64 can scale r by, which only rel_error <= 0 or an
+ *     absurdly small one lets happen.  A NaN is not frozen: b = 0 gives 0/0 in the seed and every shift runs to the cap as NaN;
+ *   - stats as for lam_hip_solve_many: the largest num_iters, all converged, the worst rel_err (NaN if any is); t_gemv and gemv_bytes
+ *     are the K = 1 product's.  num_iters / converged / rel_err: nshifts entries each, any may be NULL;
+ *   - the multi-shift solution stays readable until lam_hip_set_problem, a new matrix, or any lam_hip_set_rhs_many /
+ *     lam_hip_solve_many* / lam_hip_gemv_many* call (then LAM_HIP_ESTATE).  Independent of the single-vector state. */
+#define LAM_HIP_MAX_SHIFTS 64
+int lam_hip_solve_mshift(lam_hip_ctx *ctx, const void *b_host, int nshifts, const double *sigma, int max_iters, double rel_error,
+                         lam_hip_stats *stats, int32_t *num_iters, int32_t *converged, double *rel_err);
+/* The first nshifts solutions of the last lam_hip_solve_mshift, shift j contiguous at x_host + j*N (vector dtype).  More than were
+ * solved: LAM_HIP_EINVAL; no readable multi-shift solution: LAM_HIP_ESTATE. */
+int lam_hip_get_solution_mshift(lam_hip_ctx *ctx, int nshifts, void *x_host);
+/* rel_res[j] = ||b - (A + s_j I) x_j||_2 / ||b||_2 for the first nshifts shifts, formed on the device per group of 8 shifts: ONE
+ * K = 8 batched product of the group's x with the group's shifts, then one pass b - y against the single b (rounded to the vector
+ * dtype, fp64 sums; plain IEEE, b = 0 gives 0/0).  Leaves the seed's batch (B, X) and the multi-shift solution readable. */
+int lam_hip_true_residual_mshift(lam_hip_ctx *ctx, int nshifts, double *rel_res);
 
 /* ---- single operators (reference private members / CUDA kernels, for parity tests, roofline
  *      probes and callers that want the BLAS pieces) ------------------------------------------ */
