@@ -165,7 +165,15 @@ int lam_hip_generate_tridiag(lam_hip_ctx *ctx);
 /* Dense symmetric strictly diagonally dominant SPD test matrix, generated on device from a
  * counter-based hash (no reference counterpart; replaces the MKL-based
  * challenge/main/random_spd_system.cpp for sizes that do not fit a file):
- *   A[i][j] = A[j][i] = u(seed,min,max)/N, u in [-1,1);  A[i][i] = 1 + (cond-1)*v(seed,i), v in [0,1)
+ * with sm = SplitMix64's output function, u01(h) = (h >> 11) * 2^-53, all index arithmetic in wrapping uint64, lo / hi the
+ * smaller / larger of the GLOBAL indices i, j:
+ *   A[i][j] = A[j][i] = (2 u01(sm(seed + sm(lo*N + hi))) - 1) * fl(1/N)   in [-1/N, 1/N)   (`+`, one rounding: the product)
+ *   A[i][i] = 1 + (cond-1) * u01(sm(seed ^ sm(2*i + 1)))                  in [1, cond)     (`^`; may be contracted into an fma)
+ * ([1, cond) in exact arithmetic; the rounded sum can reach cond itself), computed in fp64 and rounded once to fp32 storage.
+ * bf16 storage is written __float2bfloat16((float)v): the compiler may keep the two roundings or merge them into ONE rounding of
+ * the fp64 value to the nearest-even bf16; either is the law, for the whole matrix (today's gfx950 compiler merges them, and 8
+ * elements per million differ from the fp32 matrix rounded to bf16).  tests/generator_model.py states the law in numpy and
+ * tests/test_gpu_generators.py holds every element of the device's matrix to it.
  * eigenvalues lie in (0, cond+1): `cond` spreads the spectrum so CG does not converge at once. */
 int lam_hip_generate_random_spd(lam_hip_ctx *ctx, uint64_t seed, double cond);
 
@@ -186,7 +194,8 @@ int lam_hip_set_rhs(lam_hip_ctx *ctx, const void *b_host);
  * challenge/main/random_spd_system.cpp:160-185). */
 int lam_hip_get_rhs(lam_hip_ctx *ctx, void *b_host);
 int lam_hip_generate_rhs(lam_hip_ctx *ctx, double value);          /* b == value (reference: 1.0) */
-int lam_hip_generate_random_rhs(lam_hip_ctx *ctx, uint64_t seed);  /* b ~ U[-1,1) */
+/* b[i] = TV(2 u01(sm(seed ^ sm(0xB5 + i))) - 1) in [-1,1), i the GLOBAL row, sm / u01 as above (tests/generator_model.py) */
+int lam_hip_generate_random_rhs(lam_hip_ctx *ctx, uint64_t seed);
 
 /* ---- the hot path ------------------------------------------------------------------------- */
 

@@ -274,8 +274,9 @@ def test_spectrum_generator_has_the_prescribed_spectrum(lam, oracle, dtype_name,
     if n % 4 == 0:
         assert np.array_equal(mats[0], mats[1])                   # the sharding does not show
     else:
-        # odd N runs the any-alignment GEMV, whose per-row peel depends on the row's ADDRESS: w = A v differs in the last
-        # bits between shardings, and so does the matrix
+        # rows are padded to a 16-byte pitch at any N, so odd N runs the aligned GEMV as well and the shardings agree bit for bit
+        # here too (tests/test_gpu_generators.py asserts it at (513, 3), (257, 6), (1025, 2) in fp64 and fp32); this older, wider gate
+        # dates from unpadded rows, when odd N ran an any-alignment GEMV whose per-row peel depended on the row's ADDRESS
         assert np.max(np.abs(mats[0].astype(np.float64) - mats[1])) <= 1e-13 * eig.max()
     assert np.array_equal(A, A.T)                                 # symmetric bit for bit
     if k > 0:
