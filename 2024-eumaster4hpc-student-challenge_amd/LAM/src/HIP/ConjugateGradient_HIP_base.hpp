@@ -345,6 +345,36 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         else _shifts.clear();
         _shifts_pending = true;
     }
+    // Batched MINRES (lam_hip_solve_many_minres): (A + sigma[j] I) x_j = b_j for shifts of EITHER sign, from x = 0, no
+    // preconditioner; arguments and results as solve_many's.  sigma != null: nrhs shifts, which BECOME the kept shifts as if
+    // set_shifts_many had been called (true_residual_many then measures under them; a CG member called afterwards hands them to
+    // lam_hip_set_shifts_many, which refuses a negative one -- CG is the wrong method there).  sigma == null: the kept shifts, or
+    // none.  A member of its own for solve_many's reason: only programs that call it need an ABI that has the entry point.
+    bool solve_many_minres(int nrhs, const FloatingType *B, const double *sigma, FloatingType *X, int max_iters, FloatingType rel_error,
+                           int32_t *num_iters = nullptr, int32_t *converged = nullptr, double *rel_err = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        _shifts_pending = true;        // the right-hand sides cleared the library's; a refusal below leaves it so
+        // the shifts this call runs under: the caller's, else the kept ones.  The caller's are kept only once the library has accepted
+        // them: a refused sigma (a NaN, an overflow in fp32) leaves the kept shifts as they were
+        const std::vector<double> use = sigma != nullptr && nrhs > 0 ? std::vector<double>(sigma, sigma + nrhs) : _shifts;
+        if (!use.empty() && (int)use.size() != nrhs) {
+            fprintf(stderr, "LAM HIP: solve_many_minres: %d shifts are kept, but %d right-hand sides are given\n", (int)use.size(), nrhs);
+            return false;
+        }
+        lam_hip_stats st;
+        if (lam_hip_solve_many_minres(_ctx, use.empty() ? nullptr : use.data(), max_iters, (double)rel_error, &st, num_iters, converged,
+                                      rel_err) != 0)
+            return report("solve_many_minres");
+        _shifts = use;
+        _shifts_pending = false;       // the call itself put them in force
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        _batch_failed = false;
+        return st.converged != 0;
+    }
     bool batch_failed() const { return _batch_failed; }      // the last solve_many* / true_residual_many call returned an error
     // ||b_j - A x_j|| / ||b_j|| of the first nrhs columns of the last batched solution, one batched product
     // (lam_hip_true_residual_many); the solution stays readable and continuable

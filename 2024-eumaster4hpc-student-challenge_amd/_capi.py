@@ -133,6 +133,8 @@ def lib():
                                        C.POINTER(C.c_double)], i32),
             "lam_hip_true_residual_many": ([vp, i32, C.POINTER(C.c_double)], i32),
             "lam_hip_set_shifts_many": ([vp, i32, C.POINTER(C.c_double)], i32),
+            "lam_hip_solve_many_minres": ([vp, C.POINTER(C.c_double), i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_double)], i32),
             "lam_hip_get_diagonal": ([vp, vp], i32),
             "lam_hip_get_solution_many": ([vp, i32, vp], i32),
             "lam_hip_gemv_many": ([vp, i32, vp, vp], i32),
@@ -511,6 +513,32 @@ class Solver:
         self.stats = st.asdict()
         self.num_iters_many, self.converged_many, self.rel_err_many = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
         return self.converged_many
+
+    def solve_minres(self, max_iters, rel_error, shifts=None):
+        """Independent MINRES recurrences on (A + shifts[j] I) x_j = b_j for the right-hand sides of set_rhs_many
+        (lam_hip_solve_many_minres): shifts of either sign, always from x = 0, no preconditioner.  shifts=None: the shifts in force;
+        else one finite number per right-hand side, which become the shifts in force (true_residuals() measures under them, and
+        solve_many refuses to run while one of them is negative).  Returns and fills what solve_many does."""
+        k = getattr(self, "nrhs", 0)
+        ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        st = Stats()
+        sg = None
+        if shifts is not None:
+            sg = np.ascontiguousarray(np.atleast_1d(shifts), dtype=np.float64)
+            assert sg.ndim == 1 and sg.size == k, "one shift per right-hand side of set_rhs_many"
+        self._chk(self._L.lam_hip_solve_many_minres(self._h, None if sg is None else sg.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    max_iters, rel_error, C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    cv.ctypes.data_as(C.POINTER(C.c_int32)), re.ctypes.data_as(C.POINTER(C.c_double))))
+        self.stats = st.asdict()
+        self.num_iters_many, self.converged_many, self.rel_err_many = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
+        return self.converged_many
+
+    def solve_shifted_minres(self, b, shifts, max_iters, rel_error):
+        """(A + shifts[j] I) x_j = b for 1..MAX_RHS shifts of either sign in one MINRES batch: b replicated as solve_shifted does."""
+        sg = np.atleast_1d(np.asarray(shifts, dtype=np.float64))
+        b = np.ascontiguousarray(b, dtype=self.vec_dtype).reshape(1, -1)
+        self.set_rhs_many(np.repeat(b, sg.size, axis=0))
+        return self.solve_minres(max_iters, rel_error, sg)
 
     def solutions(self):
         """(nrhs, N): row j is the solution of right-hand side j of the last solve_many."""

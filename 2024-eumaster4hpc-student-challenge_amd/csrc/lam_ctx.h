@@ -98,8 +98,15 @@ struct MshiftState {
     bool valid = false;          // the multi-shift solution is readable: cleared by whatever clears or replaces the batch's
 };
 
+// lam_hip_solve_many_minres: what MINRES needs beyond the batch's own vectors (its v is the batch's P, u its AP, v_old its R).
+// Allocated by the first MINRES call for the batch's n (minres_ensure), released with the batch (multi_release).
+struct MinresState {
+    void *W = nullptr, *WOLD = nullptr;      // (n + 16) * kMaxRhs elements each
+    MinresScalars *sc = nullptr;             // device; the last of the three to be allocated: set means all are
+};
+
 struct MultiState {
-    uint64_t n = 0;              // the problem size the buffers were allocated for (0: none)
+    uint64_t n = 0;             // the problem size the buffers were allocated for (0: none)
     void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out
     double *part_gemv = nullptr; // [kMaxRhs][n]: p_j.Ap_j partials per product workgroup
@@ -116,9 +123,11 @@ struct MultiState {
     int last_K = 0;              // option "multi_rhs_k": the K the last batched call ran
     // lam_hip_set_shifts_many: column j is the system (A + shift[j] I) x_j = b_j.  Each value is exactly a value of the vector dtype;
     // shifted == some shift[j] != 0, and only then do the SHIFT instantiations run.  Cleared with the right-hand sides.
+    // Negative values come from lam_hip_solve_many_minres alone, and the CG entry points refuse to run under them.
     double shift[kMaxRhs] = {};
     bool shifted = false;
     MshiftState ms;
+    MinresState mr;
 };
 
 // Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,

@@ -2934,6 +2934,243 @@ multi_deinterleave_kernel(const TV *__restrict__ inter, int ncols, TV *__restric
             if (j < ncols) cols[(uint64_t)j * n + i] = inter[i * K + j];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Batched MINRES (lam_hip_solve_many_minres, lam_multi.h): K independent Paige-Saunders recurrences on (A + s_j I) x_j = b_j, shifts
+// of either sign, advanced together.  Three launches per iteration: multi_gemv_kernel on V (u = (A + s I) v, partials of v.u),
+// minres_lanczos_kernel (alpha = v.u ; u -= alpha v + beta v_old ; partials of u.u) and minres_update_kernel (the rotation's
+// scalars, w, x, the stop test, v_old = v, v = u / beta').  The recurrence is stated in include/lam_hip.h.
+// Vectors: V is the batch's P (the product's input: zero behind row n), U its AP, v_old its R, X its X; W and W_OLD are MINRES' own.
+// Scalars: the MultiScalars prefix (what the product kernel reads and the host knows) with col[j].bb = b.b, .alpha = the last v.u,
+// .beta = the last beta', .iters, .stop; behind it the rotation's state in a ring of two, iteration k reading slot (k + 1) & 1 and
+// workgroup 0 writing slot k & 1, so no workgroup of a launch reads what that launch writes (CgScalars::rr's scheme).
+// Who decides: every workgroup of minres_update_kernel recomputes the column's scalars and its stop decision from bits nobody writes
+// in that launch; workgroup 0 alone stores them.  A column that stops at k still takes iteration k's w and x update, so "does this
+// column run" cannot be col[j].stop, which a workgroup that starts late would find raised: frozen_at[j] is the first iteration in
+// which the column does nothing (0: live; k + 1 for a stop at k; 1 for a padding column), one word, and the late workgroup reads
+// "ran at k" either way -- multi_p_kernel's argument with mshift_step_kernel's word.  For the same reason minres_update_kernel does
+// not return on all_stop, which its own workgroup 0 raises while the stopping iteration's update is still owed: it returns when no
+// column runs at k by frozen_at.  The product and minres_lanczos_kernel keep the all_stop guard: neither launch writes it.
+// The coefficients that multiply vectors (alpha, beta, eps_old, delta, 1 / gamma, phi, 1 / beta', 1 / beta1) are formed in fp64 and
+// rounded to the vector dtype once per column and iteration; every vector statement is an explicit fma_tv chain, so which operand is
+// fused is the source's choice and not the compiler's.
+// ---------------------------------------------------------------------------------------------
+struct MinresRot {                // one ring slot
+    double beta, cs, sn, dbar, eps, phibar;
+};
+struct MinresScalars : MultiScalars {
+    double beta1[kMaxRhs];        // sqrt(b.b)
+    MinresRot rot[kMaxRhs][2];    // after iteration k at [k & 1]; a stopped column's final state is at [iters & 1]
+    double rel_err[kMaxRhs];      // phibar / beta1 of the last completed iteration (the start: beta1 / beta1)
+    int frozen_at[kMaxRhs];       // 0: live; else the first iteration in which the column does nothing
+};
+
+// x = v_old = w = w_old = 0 ; per-workgroup partials of b_j.b_j at [j * gridDim.x + block] ; V's rows behind row n zero in this K's
+// layout (see multi_init_kernel)
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+minres_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__ VOLD, TV *__restrict__ W, TV *__restrict__ WOLD,
+                   TV *__restrict__ V, uint64_t n, double *__restrict__ partial)
+{
+    __shared__ double s_red[kWaves];
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = 0.0;
+    if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) V[n * K + threadIdx.x] = (TV)0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t e = i * K + j;
+            const TV bi = B[e];
+            X[e] = (TV)0; VOLD[e] = (TV)0; W[e] = (TV)0; WOLD[e] = (TV)0;
+            acc[j] += (double)bi * (double)bi;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// per column: bb, beta1 = sqrt(bb), the rotation's start (beta = 0, cs = -1, sn = 0, dbar = 0, eps = 0, phibar = beta1) in slot 0,
+// iters = 0; live columns start running, padding columns are born stopped.  One workgroup.
+template <int K>
+__global__ void __launch_bounds__(kBlock)
+minres_init_scalars_kernel(const double *__restrict__ red, int nred, int nrhs, MinresScalars *sc, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    for (int j = 0; j < kMaxRhs; j++) {
+        const double t = j < K ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        if (threadIdx.x == 0) {
+            const double beta1 = sqrt(t);
+            CgScalars &c = sc->col[j];
+            c.bb = t; c.rr[0] = 0.0; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
+            c.stop = j < nrhs ? 0 : 1;
+            sc->beta1[j] = beta1;
+            MinresRot r0;
+            r0.beta = 0.0; r0.cs = -1.0; r0.sn = 0.0; r0.dbar = 0.0; r0.eps = 0.0; r0.phibar = beta1;
+            sc->rot[j][0] = r0;
+            sc->rot[j][1] = r0;
+            sc->rel_err[j] = beta1 / beta1;
+            sc->frozen_at[j] = j < nrhs ? 0 : 1;
+        }
+    }
+    if (threadIdx.x == 0) {
+        sc->pad = 0;
+        sc->all_stop = 0;
+        post_progress(host_flags, 0, false);
+    }
+}
+
+// v_j = b_j * (1 / beta1_j) for the live columns, 0 for the padding columns (the product multiplies them like any other)
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+minres_start_kernel(const TV *__restrict__ B, TV *__restrict__ V, uint64_t n, const MinresScalars *sc)
+{
+    TV ib[K];
+    bool live[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        live[j] = sc->frozen_at[j] == 0;
+        ib[j] = (TV)(1.0 / sc->beta1[j]);
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t e = i * K + j;
+            V[e] = live[j] ? B[e] * ib[j] : (TV)0;
+        }
+    }
+}
+
+// vector launch 1, per running column j: alpha = v_j.u_j from the product's partials ; u_j = (u_j - alpha v_j) - beta v_old_j ;
+// partials of u_j.u_j.  No workgroup writes what another reads: col[j].alpha is for the next launch.
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+minres_lanczos_kernel(const double *__restrict__ red, int nred, MinresScalars *sc, int k, const TV *__restrict__ V,
+                      const TV *__restrict__ VOLD, TV *__restrict__ U, uint64_t n, double *__restrict__ partial)
+{
+    __shared__ double s_red[kWaves];
+    if (sc->all_stop) return;
+    bool run[K];
+    double alpha_d[K], acc[K];
+    TV nalpha[K], nbeta[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        run[j] = sc->col[j].stop == 0;
+        alpha_d[j] = run[j] ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        nalpha[j] = -(TV)alpha_d[j];
+        nbeta[j] = -(TV)sc->rot[j][(k + 1) & 1].beta;
+        acc[j] = 0.0;
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (!run[j]) continue;
+            const uint64_t e = i * K + j;
+            const TV ui = fma_tv(nbeta[j], VOLD[e], fma_tv(nalpha[j], V[e], U[e]));
+            U[e] = ui;
+            acc[j] += (double)ui * (double)ui;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) {
+            partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            if (blockIdx.x == 0 && run[j]) { sc->col[j].pAp = alpha_d[j]; sc->col[j].alpha = alpha_d[j]; }
+        }
+    }
+}
+
+// vector launch 2, per running column j: beta' = sqrt(u_j.u_j), the rotation, w_j and x_j ; rel_err = phibar / beta1 ; below
+// rel_error the column stops (v_j untouched, its scalars final), else v_old_j = v_j, v_j = u_j * (1 / beta').  The progress word
+// reports the iteration, and "stopped" once EVERY live column has stopped.
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+minres_update_kernel(const double *__restrict__ red, int nred, MinresScalars *sc, int k, double rel_error, const TV *__restrict__ U,
+                     TV *__restrict__ V, TV *__restrict__ VOLD, TV *__restrict__ W, TV *__restrict__ WOLD, TV *__restrict__ X,
+                     uint64_t n, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    // NOT `if (sc->all_stop) return`: workgroup 0 raises all_stop in the launch in which the last live column stops, and that
+    // iteration still owes its w and x update -- a workgroup (or one wave of one) that started behind that store would skip its rows.
+    // The launch is over only if no column runs at k, which frozen_at says the same way before and after workgroup 0's store: the
+    // launches the lag rule enqueues past the batch's stop find k >= frozen_at in every column and return here, before they post.
+    bool run[K], adv[K];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const int fz = sc->frozen_at[j];
+        run[j] = fz == 0 || k < fz;
+        any = any || run[j];
+    }
+    if (!any) return;
+    TV neps[K], ndelta[K], igamma[K], phi[K], ibeta[K];
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double uu = run[j] ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        const MinresRot o = sc->rot[j][(k + 1) & 1];
+        const double alpha = sc->col[j].alpha, beta1 = sc->beta1[j];
+        const double betan = sqrt(uu);
+        MinresRot r;
+        r.beta = betan;
+        const double delta = o.cs * o.dbar + o.sn * alpha;
+        const double gbar = o.sn * o.dbar - o.cs * alpha;
+        r.eps = o.sn * betan;
+        r.dbar = -o.cs * betan;
+        const double gamma = hypot(gbar, betan);
+        r.cs = gbar / gamma;
+        r.sn = betan / gamma;
+        const double phi_d = r.cs * o.phibar;
+        r.phibar = r.sn * o.phibar;
+        const double re = r.phibar / beta1;
+        const bool stop = re < rel_error;
+        adv[j] = run[j] && !stop;
+        all = all && !adv[j];
+        neps[j] = -(TV)o.eps;
+        ndelta[j] = -(TV)delta;
+        igamma[j] = (TV)(1.0 / gamma);
+        phi[j] = (TV)phi_d;
+        ibeta[j] = (TV)(1.0 / betan);
+        if (run[j] && blockIdx.x == 0 && threadIdx.x == 0) {
+            sc->rot[j][k & 1] = r;
+            sc->rel_err[j] = re;
+            sc->col[j].beta = betan;
+            sc->col[j].iters = k;
+        }
+    }
+    // a workgroup that starts after workgroup 0 has frozen a column in THIS launch reads frozen_at = k + 1 and runs it, as workgroup
+    // 0 did; `all` is computed from the same bits everywhere, and only workgroup 0's value is used
+    if (blockIdx.x == 0) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                if (run[j] && !adv[j]) { sc->frozen_at[j] = k + 1; sc->col[j].stop = 1; }
+            if (all) sc->all_stop = 1;
+            post_progress(host_flags, k, all);
+        }
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (!run[j]) continue;
+            const uint64_t e = i * K + j;
+            const TV vi = V[e], wi = W[e];
+            const TV wn = fma_tv(ndelta[j], wi, fma_tv(neps[j], WOLD[e], vi)) * igamma[j];
+            WOLD[e] = wi;
+            W[e] = wn;
+            X[e] = fma_tv(phi[j], wn, X[e]);
+            if (adv[j]) {
+                VOLD[e] = vi;
+                V[e] = U[e] * ibeta[j];
+            }
+        }
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // Multi-shift CG (lam_hip_solve_mshift, lam_multi.h): (A + s_j I) x_j = b for up to kMaxShifts shifts and ONE b.  The shifted Krylov

@@ -15,6 +15,9 @@
 // adds s_j p_j[row]; the K shifts travel by value in its arguments) in the loop, in the guess's product and in the true residual's, and
 // under Jacobi the DK = true instantiations of the vector kernels on a K-wide dinv_k = 1 / (A_ii + s_j) (shifted_dinv_kernel).  No
 // shifts, or all of them zero: the instantiations and the launches of before.
+// lam_hip_solve_many_minres (minres_solve, next to multi_solve): K MINRES recurrences on the same product launch, shifts of either
+// sign; its own three init and two per-iteration vector kernels, W / W_OLD and scalars' block (MinresState), the loop's host side shared
+// in shape.  It alone can leave a negative shift in force, under which multi_solve refuses to run.
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
@@ -47,6 +50,7 @@ void multi_release(lam_hip_ctx *c)
     c->pcg = PcgState();
     free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.part_rr, m.res, m.sc});
     free_dev({m.ms.XS, m.ms.PS, m.ms.sc});
+    free_dev({m.mr.W, m.mr.WOLD, m.mr.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -382,6 +386,42 @@ namespace {
 // where a batched solve starts: x = 0, a guess given on the host, or the batch's own last solution
 enum MultiGuess { kGuessNone, kGuessHost, kGuessCurrent };
 
+// what a batched solve reports, CG or MINRES: the per-column arrays and the batch's stats from the scalars' prefix as the host read
+// it back; rel_of(j, col) is column j's rel_err (CG: from its r.r ring; MINRES: its own word)
+template <typename F>
+void multi_report(lam_hip_ctx *c, const MultiScalars &h, F &&rel_of, double t0, double t1, double gemv_ms, int samples, lam_hip_stats *st,
+                  int32_t *num_iters, int32_t *converged, double *rel_err)
+{
+    const MultiState &m = c->multi;
+    int ran = 0, batch_iters = 0, all_conv = 1;
+    double worst = 0.0;
+    bool any_nan = false;
+    for (int j = 0; j < m.nrhs; j++) {
+        const CgScalars &sc = h.col[j];
+        const int ni = sc.stop ? sc.iters : sc.iters + 1;
+        const double re = rel_of(j, sc);
+        if (num_iters) num_iters[j] = ni;
+        if (converged) converged[j] = sc.stop != 0;
+        if (rel_err) rel_err[j] = re;
+        ran = std::max(ran, sc.iters);
+        batch_iters = std::max(batch_iters, ni);
+        all_conv = all_conv && sc.stop != 0;
+        if (re != re) any_nan = true; else worst = std::max(worst, re);
+    }
+    if (st) {
+        memset(st, 0, sizeof *st);
+        st->num_iters = batch_iters;
+        st->converged = all_conv;
+        st->rel_err = any_nan ? std::nan("") : worst;
+        st->t_total = t1 - t0;
+        st->t_iter = ran > 0 ? (t1 - t0) / ran : 0.0;
+        st->t_gemv = samples > 0 ? gemv_ms * 1e-3 / samples : 0.0;
+        st->t_comm_init = c->t_comm_init;
+        // the product launch alone, with or without the preconditioner: the diagonal is read by the two vector launches
+        st->gemv_bytes = (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n;
+    }
+}
+
 // lam_hip_solve_many (precond = LAM_HIP_PC_NONE), lam_hip_solve_many_pc and lam_hip_solve_many_x0: one body, one sequence of
 // launches.  The Jacobi-preconditioned batch runs the PC = true instantiations of the four vector kernels on dinv and a second
 // partial array (both null for the plain batch); the product launch, the scalars' block, the progress word, the lag rule and the
@@ -403,6 +443,11 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
         return fail(c, LAM_HIP_ESTATE, "matrix and right-hand sides (lam_hip_set_rhs_many) must be set before %s", fn);
     if (guess == kGuessCurrent && !m.solved)
         return fail(c, LAM_HIP_ESTATE, "%s: x0_host is NULL and there is no batched solution to continue from (lam_hip_solve_many)", fn);
+    // only lam_hip_solve_many_minres leaves a negative shift in force; nothing is touched, the batched solution stays readable
+    for (int j = 0; j < m.nrhs; j++)
+        if (m.shift[j] < 0.0)
+            return fail(c, LAM_HIP_EINVAL, "%s: shift %d in force is %g: CG needs every shift >= 0 (a negative one can make the matrix "
+                        "indefinite); use lam_hip_solve_many_minres, or replace the shifts (lam_hip_set_shifts_many)", fn, j, m.shift[j]);
     const double t0 = now_s();
     ShardBase &s0 = c->sh[0];
     LAMCHK(set_dev(c, s0));
@@ -507,34 +552,124 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
     HIPCHK(c, hipMemcpyAsync(m.sc_host, m.sc, sizeof(MultiScalars), hipMemcpyDeviceToHost, s0.stream));
     HIPCHK(c, hipStreamSynchronize(s0.stream));
     m.solved = true;
-    const double t1 = now_s();
-    int ran = 0, batch_iters = 0, all_conv = 1;
-    double worst = 0.0;
-    bool any_nan = false;
-    for (int j = 0; j < m.nrhs; j++) {
-        const CgScalars &sc = m.sc_host->col[j];
-        const int ni = sc.stop ? sc.iters : sc.iters + 1;
-        const double re = std::sqrt(sc.rr[sc.iters & 1] / sc.bb);
-        if (num_iters) num_iters[j] = ni;
-        if (converged) converged[j] = sc.stop != 0;
-        if (rel_err) rel_err[j] = re;
-        ran = std::max(ran, sc.iters);
-        batch_iters = std::max(batch_iters, ni);
-        all_conv = all_conv && sc.stop != 0;
-        if (re != re) any_nan = true; else worst = std::max(worst, re);
+    multi_report(c, *m.sc_host, [](int, const CgScalars &sc) { return std::sqrt(sc.rr[sc.iters & 1] / sc.bb); }, t0, now_s(), gemv_ms, samples,
+                 st, num_iters, converged, rel_err);
+    return 0;
+}
+
+// W, W_OLD and the scalars of lam_hip_solve_many_minres for the batch's n (multi.n == n has been checked)
+int minres_ensure(lam_hip_ctx *c)
+{
+    MinresState &r = c->multi.mr;
+    if (r.sc) return 0;
+    free_dev({r.W, r.WOLD});                 // what a failed attempt left: it is retried, never launched on
+    r = MinresState();
+    const size_t bytes = (size_t)(c->n + kMultiPadRows) * kMaxRhs * c->esz_v();
+    HIPCHK(c, hipMalloc(&r.W, bytes));
+    HIPCHK(c, hipMalloc(&r.WOLD, bytes));
+    HIPCHK(c, hipMalloc((void **)&r.sc, sizeof(MinresScalars)));
+    HIPCHK(c, hipMemsetAsync(r.sc, 0, sizeof(MinresScalars), c->sh[0].stream));
+    return 0;
+}
+
+// lam_hip_solve_many_minres: multi_solve's sibling.  The same enqueue loop -- the batch's progress word under the lag rule, the timed
+// product slots, the stats -- around MINRES' own vector launches and scalars' block; the product launch is the batch's, with V (the
+// batch's P) as its input.  multi_solve launches what it launched before.
+int minres_solve(lam_hip_ctx *c, const char *fn, const double *sigma, int max_iters, double rel_error, lam_hip_stats *st,
+                 int32_t *num_iters, int32_t *converged, double *rel_err)
+{
+    LAMCHK(multi_supported(c, fn));
+    if (max_iters < 0) return fail(c, LAM_HIP_EINVAL, "max_iters must be >= 0");
+    MultiState &m = c->multi;
+    if (!c->have_matrix || !m.have_rhs || m.n != c->n)
+        return fail(c, LAM_HIP_ESTATE, "matrix and right-hand sides (lam_hip_set_rhs_many) must be set before %s", fn);
+    double s[kMaxRhs] = {};
+    bool any = false;
+    if (sigma) {
+        for (int j = 0; j < m.nrhs; j++) {
+            const double r = c->dtype == LAM_HIP_F32 ? (double)(float)sigma[j] : sigma[j];
+            if (!std::isfinite(sigma[j]) || !std::isfinite(r))
+                return fail(c, LAM_HIP_EINVAL, "%s: shift %d is %g: every shift must be finite, in the vector dtype too", fn, j, sigma[j]);
+            s[j] = r;
+            any = any || r != 0.0;
+        }
     }
-    if (st) {
-        memset(st, 0, sizeof *st);
-        st->num_iters = batch_iters;
-        st->converged = all_conv;
-        st->rel_err = any_nan ? std::nan("") : worst;
-        st->t_total = t1 - t0;
-        st->t_iter = ran > 0 ? (t1 - t0) / ran : 0.0;
-        st->t_gemv = samples > 0 ? gemv_ms * 1e-3 / samples : 0.0;
-        st->t_comm_init = c->t_comm_init;
-        // the product launch alone, with or without the preconditioner: the diagonal is read by the two vector launches
-        st->gemv_bytes = (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n;
+    const double t0 = now_s();
+    ShardBase &s0 = c->sh[0];
+    LAMCHK(set_dev(c, s0));
+    HIPCHK(c, hipStreamSynchronize(s0.stream));
+    // the lazy allocation first: if it fails, the shifts in force and the batched solution are what they were
+    LAMCHK(minres_ensure(c));
+    if (sigma) {
+        memcpy(m.shift, s, sizeof s);
+        m.shifted = any;
     }
+    m.solved = false;
+    m.ms.valid = false;
+    MinresState &mr = m.mr;
+    const double *const shift = m.shifted ? m.shift : nullptr;
+    m.host_flags[0] = m.host_flags[1] = 0;
+    for (int i = 0; i < kLag; i++) m.timed_slot[i] = false;
+    c->prog_t = 0.0;
+    c->multi.last_K = m.K;
+    ShardBase view;
+    view.dev = s0.dev; view.stream = s0.stream; view.host_flags = m.host_flags;
+    const int vb = vec_grid(c->n), gb = multi_gemv_grid(c);
+    double gemv_ms = 0.0;
+    int samples = 0, enq = 0;
+    LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc) -> int {
+        using I = decltype(impl);
+        using TA = typename ImplTraits<I>::TA;
+        using TV = typename ImplTraits<I>::TV;
+        constexpr int K = decltype(kc)::value;
+        TV *const V = (TV *)m.P, *const U = (TV *)m.AP, *const VOLD = (TV *)m.R, *const X = (TV *)m.X;
+        TV *const W = (TV *)mr.W, *const WOLD = (TV *)mr.WOLD;
+        hipLaunchKernelGGL((minres_init_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, X, VOLD, W, WOLD, V, c->n,
+                           m.part_vec);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((minres_init_scalars_kernel<K>), dim3(1), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, m.nrhs,
+                           mr.sc, (volatile int *)m.host_flags);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((minres_start_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const TV *)m.B, V, c->n,
+                           (const MinresScalars *)mr.sc);
+        HIPCHK(c, hipGetLastError());
+        for (int i = 0; i < max_iters; i++) {
+            const int k = i + 1, slot = i % kLag;
+            if (i >= kLag) {
+                const int d = lag_check(c, view, k);
+                if (d < 0) return d;
+                if (d != 0) break;
+                multi_harvest(m, slot, &gemv_ms, &samples);
+            }
+            const double te = now_s();
+            const bool timed = timed_iteration(c, s0, k);
+            m.timed_slot[slot] = timed;
+            if (timed) RECORD(c, m.ev0[slot], s0.stream);
+            LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)V, U, m.part_gemv, mr.sc, shift)));
+            if (timed) RECORD(c, m.ev1[slot], s0.stream);
+            hipLaunchKernelGGL((minres_lanczos_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_gemv, gb, mr.sc, k,
+                               (const TV *)V, (const TV *)VOLD, U, c->n, m.part_vec);
+            LAUNCHED(c);
+            hipLaunchKernelGGL((minres_update_kernel<TV, K>), dim3(vb), dim3(kBlock), 0, s0.stream, (const double *)m.part_vec, vb, mr.sc, k,
+                               rel_error, (const TV *)U, V, VOLD, W, WOLD, X, c->n, (volatile int *)m.host_flags);
+            LAUNCHED(c);
+            c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
+            enq++;
+        }
+        return 0;
+    }));
+    if (enq > 0) {
+        Progress pr;
+        LAMCHK(await_progress(c, view, enq, &pr, /*precise=*/true));
+    }
+    HIPCHK(c, hipStreamSynchronize(s0.stream));
+    for (int j = 0; j < kLag; j++) multi_harvest(m, j, &gemv_ms, &samples);
+    const std::unique_ptr<MinresScalars> h(new MinresScalars);
+    HIPCHK(c, hipMemcpyAsync(h.get(), mr.sc, sizeof(MinresScalars), hipMemcpyDeviceToHost, s0.stream));
+    HIPCHK(c, hipStreamSynchronize(s0.stream));
+    m.solved = true;
+    multi_report(c, *h, [&](int j, const CgScalars &) { return h->rel_err[j]; }, t0, now_s(), gemv_ms, samples, st, num_iters, converged,
+                 rel_err);
     return 0;
 }
 
@@ -562,6 +697,13 @@ int lam_hip_solve_many_x0(lam_hip_ctx *c, int precond, const void *x0_host, int 
     if (!c) return LAM_HIP_EINVAL;
     return multi_solve(c, "lam_hip_solve_many_x0", precond, x0_host ? kGuessHost : kGuessCurrent, x0_host, max_iters, rel_error, st,
                        num_iters, converged, rel_err);
+}
+
+int lam_hip_solve_many_minres(lam_hip_ctx *c, const double *sigma, int max_iters, double rel_error, lam_hip_stats *st, int32_t *num_iters,
+                              int32_t *converged, double *rel_err)
+{
+    if (!c) return LAM_HIP_EINVAL;
+    return minres_solve(c, "lam_hip_solve_many_minres", sigma, max_iters, rel_error, st, num_iters, converged, rel_err);
 }
 
 // One batched product of X (staged through P, whose rows behind row n the product needs zero), one K-wide pass over B and A X, one

@@ -1,6 +1,6 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
-//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
@@ -12,6 +12,9 @@
 // -M (with -S, which may then list up to 64 shifts): multi-shift CG (lam_hip_solve_mshift) -- ONE right-hand side, column 0's
 // constant 1, and every shift solved behind the single-column product of the smallest shift's system; one CSV line per shift in the
 // same columns, -T prints lam_hip_true_residual_mshift's values.  -M without -S, with -J or with -w is refused.
+// -m: batched MINRES (lam_hip_solve_many_minres) in place of CG, from x = 0 and without a preconditioner; with it -S takes finite
+// shifts of EITHER sign (without it a negative shift is refused as ever).  Same CSV columns; -T measures under the shifts.  -m with
+// -J, -w or -M is refused.
 // Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
@@ -30,7 +33,8 @@
 #include "LAM.hpp"
 
 template <typename T>
-static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi, int warm, bool true_res, const std::vector<double> &shifts)
+static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi, int warm, bool true_res, const std::vector<double> &shifts,
+               bool minres)
 {
     using clk = std::chrono::high_resolution_clock;
     LAM::ConjugateGradient_HIP<T> cg(0);
@@ -44,12 +48,16 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
     std::vector<T> B((size_t)nrhs * rows);
     for (int j = 0; j < nrhs; j++)
         for (size_t i = 0; i < rows; i++) B[(size_t)j * rows + i] = shifts.empty() ? (T)(double)(1u << j) : (T)1;
-    if (!shifts.empty()) cg.set_shifts_many(nrhs, shifts.data());
+    if (!shifts.empty() && !minres) cg.set_shifts_many(nrhs, shifts.data());
     std::vector<int32_t> iters(nrhs), conv(nrhs);
     std::vector<double> rel(nrhs);
     const auto t1 = clk::now();
     const int pc = jacobi ? LAM_HIP_PC_JACOBI : LAM_HIP_PC_NONE;
-    if (warm >= 0) {
+    if (minres) {
+        cg.solve_many_minres(nrhs, B.data(), shifts.empty() ? nullptr : shifts.data(), nullptr, max_iters, (T)rel_error, iters.data(),
+                             conv.data(), rel.data());
+        if (cg.batch_failed()) return 3;
+    } else if (warm >= 0) {
         // stage 1 from a zero guess (the plain solve, bit for bit), stage 2 from its solution; 0 iterations is an answer here,
         // so failure is the call's own report
         const std::vector<T> zero((size_t)nrhs * rows, (T)0);
@@ -112,15 +120,18 @@ static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_re
     return 0;
 }
 
-// "s0,s1,...": 1..LAM_HIP_MAX_SHIFTS numbers (main holds a list without -M to LAM_HIP_MAX_RHS), each finite and >= 0, nothing else
-static bool parse_shifts(const char *arg, std::vector<double> *out)
+// "s0,s1,...": 1..LAM_HIP_MAX_SHIFTS numbers (main holds a list without -M to LAM_HIP_MAX_RHS), each finite, nothing else; *negative:
+// one of them is < 0, which main accepts under -m only (it decides once every option is parsed)
+static bool parse_shifts(const char *arg, std::vector<double> *out, bool *negative)
 {
     out->clear();
+    *negative = false;
     const char *p = arg;
     for (;;) {
         char *end = nullptr;
         const double v = strtod(p, &end);
-        if (end == p || !(v >= 0.0) || !std::isfinite(v) || out->size() == (size_t)LAM_HIP_MAX_SHIFTS) return false;
+        if (end == p || !std::isfinite(v) || out->size() == (size_t)LAM_HIP_MAX_SHIFTS) return false;
+        if (v < 0.0) *negative = true;
         out->push_back(v);
         if (*end == '\0') return true;
         if (*end != ',') return false;
@@ -134,11 +145,11 @@ int main(int argc, char **argv)
     int nrhs = 1, max_iters = 1000, opt;
     double rel_error = 1e-9;
     const char *precision = "f64";
-    bool jacobi = false, true_res = false, mshift = false;
+    bool jacobi = false, true_res = false, mshift = false, minres = false, negative = false;
     int warm = -1;                  // -1: no -w
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:Mh")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:Mmh")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
@@ -148,22 +159,33 @@ int main(int argc, char **argv)
         case 'J': jacobi = true; break;
         case 'w': warm = atoi(optarg); bad_warm = warm < 0; break;
         case 'T': true_res = true; break;
-        case 'S': bad_shifts = !parse_shifts(optarg, &shifts); break;
+        case 'S': bad_shifts = !parse_shifts(optarg, &shifts, &negative); break;
         case 'M': mshift = true; break;
+        case 'm': minres = true; break;
         default:
             fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
                     "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)] "
-                    "[-M (with -S, up to %d shifts: multi-shift CG on one right-hand side; not with -J, -w)]\n", argv[0],
+                    "[-M (with -S, up to %d shifts: multi-shift CG on one right-hand side; not with -J, -w)] "
+                    "[-m (MINRES in place of CG: -S then takes finite shifts of either sign; not with -J, -w, -M)]\n", argv[0],
                     LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS);
             return opt == 'h' ? 0 : 1;
         }
     }
+    if (minres && (jacobi || warm >= 0 || bad_warm || mshift)) {
+        fprintf(stderr, "Usage: -m takes neither -J, -w nor -M: MINRES has no preconditioner, starts from x = 0 and is not multi-shift\n");
+        return 1;
+    }
+    if (negative && !minres) bad_shifts = true;      // a negative shift is MINRES' alone
     if (mshift && (shifts.empty() || bad_shifts || jacobi || warm >= 0 || bad_warm || k_given)) {
         fprintf(stderr, "Usage: -M needs -S s0,s1,... (1..%d finite shifts >= 0) and takes neither -J, -w nor -k: multi-shift CG has one "
                 "right-hand side, no preconditioner and no guess\n", LAM_HIP_MAX_SHIFTS);
         return 1;
     }
     if (!mshift && shifts.size() > (size_t)LAM_HIP_MAX_RHS) bad_shifts = true;
+    if (minres && (bad_shifts || (!shifts.empty() && k_given && nrhs != (int)shifts.size()))) {
+        fprintf(stderr, "-S takes 1..%d comma-separated finite shifts (of either sign under -m), and -k, if given, their number\n", LAM_HIP_MAX_RHS);
+        return 1;
+    }
     if (bad_shifts || (!shifts.empty() && k_given && nrhs != (int)shifts.size())) {
         fprintf(stderr, "-S takes 1..%d comma-separated finite shifts >= 0, and -k, if given, their number\n", LAM_HIP_MAX_RHS);
         return 1;
@@ -184,8 +206,8 @@ int main(int argc, char **argv)
                 argv[0], LAM_HIP_MAX_RHS);
         return 1;
     }
-    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts);
-    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts);
+    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts, minres);
+    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts, minres);
     fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
     return 1;
 }

@@ -52,7 +52,9 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): lam_hip_solve_many_x0 and lam_hip_true_residual_many.
  *      Added under version 4 likewise (purely additive): lam_hip_set_shifts_many.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_SHIFTS, lam_hip_solve_mshift, lam_hip_get_solution_mshift and
- *      lam_hip_true_residual_mshift. */
+ *      lam_hip_true_residual_mshift.
+ *      Added under version 4 likewise (purely additive): lam_hip_solve_many_minres.  One new refusal becomes reachable with it: a
+ *      CG batch call while a negative shift (which only lam_hip_solve_many_minres accepts) is in force. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -333,6 +335,55 @@ int lam_hip_true_residual_many(lam_hip_ctx *ctx, int nrhs, double *rel_res);
  *   - stats, gemv_bytes, the per-column arrays, frozen columns, NaN confinement, max_iters + 1 at the cap, the born-stopped
  *     column at k = 0 and "multi_rhs_k" are unchanged.  No launch, no device traffic: the shifts travel in the kernel arguments. */
 int lam_hip_set_shifts_many(lam_hip_ctx *ctx, int nrhs, const double *sigma);
+/* Batched MINRES (Paige and Saunders): (A + s_j I) x_j = b_j for shifts of EITHER sign -- shift-and-invert and inverse iteration
+ * inside the spectrum, resolvents, frequency sweeps, any symmetric system that is not positive definite -- on the right-hand sides of
+ * the last lam_hip_set_rhs_many, up to 8 columns with different shifts per pass over A.  Three launches per iteration: the batch's
+ * product (its SHIFT epilogue does not care about the sign), one vector launch that ends in a norm, one that consumes it.  On SPD
+ * systems it is useful too: rel_err decreases monotonically and in exact arithmetic IS the true residual norm, which CG's recursive
+ * residual is not.  No reference counterpart.
+ *   - always from x = 0 and without a preconditioner: Jacobi with diag(A) + s_j is not positive definite once shifts may be negative,
+ *     and MINRES needs an SPD preconditioner.  Out of scope likewise: an initial guess, multi-shift MINRES, several shards, bf16;
+ *   - sigma == NULL: the shifts in force (none, or lam_hip_set_shifts_many's).  sigma != NULL: nrhs (of lam_hip_set_rhs_many) shifts
+ *     of any sign, each finite and finite after rounding to the vector dtype; anything else is LAM_HIP_EINVAL naming the column and
+ *     the value, and the shifts in force stay.  Accepted shifts BECOME the shifts in force: lam_hip_true_residual_many then measures
+ *     b_j - (A + s_j I) x_j under them and lam_hip_get_solution_many reads X.  All shifts zero after rounding: the unshifted product;
+ *   - existing calls behave as before: lam_hip_set_shifts_many keeps refusing a negative shift, and it, lam_hip_set_rhs_many,
+ *     lam_hip_set_problem and lam_hip_solve_mshift replace or clear the shifts as they always did.  NEW: lam_hip_solve_many, _pc and
+ *     _x0 while a negative shift is in force are refused -- LAM_HIP_EINVAL naming the column and the value, nothing iterated, the
+ *     batched solution still readable;
+ *   - the recurrence, per column, all scalars fp64:
+ *         bb = b.b ; beta1 = sqrt(bb) ; v = b / beta1 ; v_old = w = w_old = x = 0
+ *         beta = 0 ; cs = -1 ; sn = 0 ; dbar = 0 ; eps = 0 ; phibar = beta1
+ *         k = 1..max_iters:
+ *            u      = (A + s I) v                 product launch; alpha = v.u from its fused partials
+ *            u     -= alpha v + beta v_old        vector launch 1; partials of u.u
+ *            beta'  = sqrt(u.u)                   vector launch 2, scalars first:
+ *            eps_o = eps ; delta = cs dbar + sn alpha ; gbar = sn dbar - cs alpha ; eps = sn beta' ; dbar = -cs beta'
+ *            gamma = hypot(gbar, beta') ; cs = gbar / gamma ; sn = beta' / gamma ; phi = cs phibar ; phibar = sn phibar
+ *            w_new  = (v - eps_o w_old - delta w) / gamma ; w_old = w ; w = w_new ; x += phi w
+ *            rel_err = phibar / beta1 ; if rel_err < rel_error: the column stops (v untouched, scalars final)
+ *            else v_old = v ; v = u / beta' ; beta = beta'
+ *     alpha is the product's fused v.(A v), NOT v.(A v - beta v_old): equal in exact arithmetic (v.v_old = 0), and the other would
+ *     cost a fourth launch.  The coefficients that multiply vectors -- alpha, beta, eps_o, delta, phi and the reciprocals 1 / beta1,
+ *     1 / gamma, 1 / beta' (the divisions above are multiplications by these) -- are rounded to the vector dtype once per column and
+ *     iteration; the vector statements are fma chains: u = fma(-beta, v_old, fma(-alpha, v, u)),
+ *     w_new = fma(-delta, w, fma(-eps_o, w_old, v)) * (1 / gamma), x = fma(phi, w_new, x).  Plain IEEE, no special case: beta' = 0
+ *     (b in an invariant subspace) gives phibar = 0 and the column stops with rel_err = 0; a singular A + s_j I never meets the test
+ *     and runs to the cap;
+ *   - everything else is lam_hip_solve_many's, with the same codes and words: several shards, rank mode, LAM_HIP_BF16 (LAM_HIP_EINVAL),
+ *     no matrix or no right-hand sides (LAM_HIP_ESTATE), max_iters < 0; stats, the per-column arrays, "multi_rhs_k" and K in
+ *     {1, 2, 4, 8} with zero padding columns born stopped; a stopped column's x and scalars never change again; a NaN or an Inf stays
+ *     in its column; b_j = 0 gives 0/0 and runs to the cap as NaN; rel_error <= 0 never stops; at the cap num_iters = max_iters + 1;
+ *     max_iters = 0 returns x = 0, converged = 0, num_iters = 1, rel_err = 1.  The batch state afterwards is a batched solution:
+ *     lam_hip_solve_many_x0(..., NULL, ...) may continue from it when no negative shift is in force;
+ *   - cost: 2 K-wide vectors (w, w_old) and a block of scalars beyond the batch's, allocated by the first call.  Per iteration the two
+ *     vector launches move about 14 K N elements (CG's: 9 K N) against N^2 for the product: 0.2 % at K = 8, N = 65536.  Measured on
+ *     one MI355X against lam_hip_solve_many of the same build and K, the two alternated in one process (tools/minres_probe.py,
+ *     profiles/minres_probe.txt): 0.999 / 1.000 / 1.004 x CG's seconds per iteration at K = 1 / 4 / 8 for fp64
+ *     N = 65536 (4.86 / 5.43 / 9.23 ms) and 1.000 / 1.000 / 1.001 x for fp32 N = 131072; under shifts of both signs (the SHIFT
+ *     product) 0.999 ... 1.007 x.  The windows of one figure spread by 0.06 ... 0.22 %. */
+int lam_hip_solve_many_minres(lam_hip_ctx *ctx, const double *sigma, int max_iters, double rel_error, lam_hip_stats *stats,
+                              int32_t *num_iters, int32_t *converged, double *rel_err);
 /* The stored diagonal A[i][i], N elements of the vector dtype (LAM_HIP_BF16 storage: the stored bf16 values as float, exactly),
  * extracted on the device(s) from the pitched matrix.  Single-process contexts with any number of shards, every storage type;
  * rank mode: LAM_HIP_EINVAL; no matrix set: LAM_HIP_ESTATE.  No reference counterpart: the reference is un-preconditioned
