@@ -1,4 +1,5 @@
-// lam_exchange.h -- context creation and the exchanges between shards: event-ordered peer stores, RCCL, the direct (in-kernel flag) exchange, gather-Ap.
+// lam_exchange.h -- context creation and the exchanges between shards: event-ordered peer stores, RCCL, the direct (in-kernel flag) exchange, gather-Ap;
+// the iteration's product step, written once for all of them: timed_product (the timing bracket), launch_split_gemv (own-slice panel, hand-over of p, the rest), gather_ap_product.
 // Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 #pragma once
 
@@ -262,18 +263,6 @@ int xt_end(lam_hip_ctx *c, ShardBase &s, hipStream_t st)
 // Does the producer launch of this dot product carry a reducer workgroup (lam_kernels.h, Finalize)?  The
 // symmetric product's second pass writes plain per-workgroup partials of p.Ap: its consumer sums them.
 bool producer_reduces(const lam_hip_ctx *c, bool second) { return c->opt_finalize != 0 && (second || !c->symv_active()); }
-
-Finalize no_finalize(const lam_hip_ctx *c)
-{
-    Finalize f;
-    f.active = 0;
-    f.mail = 0;
-    f.seq = 0;
-    f.dst.n = 0;
-    f.slot = 0;
-    f.host_err = c ? c->direct_err : nullptr;
-    return f;
-}
 
 // Where the reduced partial of shard `s` goes (see lam_kernels.h, Finalize): slot `index` of the
 // gather array of every local shard (one process: peer stores) or of this rank (rank mode).
@@ -649,6 +638,42 @@ bool timed_iteration(const lam_hip_ctx *c, const ShardBase &s, int k)
     return c->opt_gemv_timing > 0 && (k - 1) % c->opt_gemv_timing == 0;
 }
 
+// ---- the product step of an iteration, written once (every exchange's enqueue code launches its product through these) --------
+// The timing bracket: `launch` runs between the event pair of ring slot `slot` when iteration k is timed, and the slot's bookkeeping
+// (timed_slot, split_slot: what harvest_shard reads) is kept here.  A product in two panels brackets each one, the second with
+// `second` (ev_g2 / ev_g3), so that t_gemv is kernel time and not what happens between the panels.  Touches the shard only: each of
+// the tuning build's enqueue threads calls it for its own shard.
+template <typename F>
+int timed_product(lam_hip_ctx *c, ShardBase &s, int k, int slot, bool second, F &&launch)
+{
+    const bool timed = timed_iteration(c, s, k);
+    if (second) s.split_slot[slot] = true;
+    else { s.timed_slot[slot] = timed; s.split_slot[slot] = false; }
+    if (timed) RECORD(c, second ? s.ev_g2[slot] : s.ev_g0[slot], s.stream);
+    LAMCHK(launch());
+    if (timed) RECORD(c, second ? s.ev_g3[slot] : s.ev_g1[slot], s.stream);
+    return 0;
+}
+
+// Ap = A p of one shard on the exchanges that hand p over (events / RCCL: phase_gemv; in-kernel flags: enqueue_shard_direct).  With
+// an own-slice panel [lo, hi) that panel comes first -- it needs only the p slice this shard wrote itself --, then `between`, the
+// step behind which the peers' slices are in (a stream wait; a kernel that waits for their flags), then the remaining columns with
+// the reducer workgroup `fin`.  lo == hi: `between`, then the whole GEMV.
+template <typename I, typename F>
+int launch_split_gemv(lam_hip_ctx *c, ShardBase &s, int k, int slot, uint64_t lo, uint64_t hi, const Finalize &fin, F &&between)
+{
+    using TV = typename ImplTraits<I>::TV;
+    const TV *p = (const TV *)s.p;
+    TV *y = (TV *)s.Ap;
+    if (hi > lo) {
+        LAMCHK(timed_product(c, s, k, slot, false, [&] { return I::launch_gemv(c, s, p, y, nullptr, s.sc, 1, lo, hi); }));
+        LAMCHK(between());
+        return timed_product(c, s, k, slot, true, [&] { return I::launch_gemv(c, s, p, y, s.part_gemv, s.sc, 2, lo, hi, &fin); });
+    }
+    LAMCHK(between());
+    return timed_product(c, s, k, slot, false, [&] { return I::launch_gemv(c, s, p, y, s.part_gemv, s.sc, 0, 0, 0, &fin); });
+}
+
 // Can a launch of `blocks` workgroups of update_fused_kernel be resident all at once?  Its workgroups wait for each
 // other inside the launch (compute workgroups for the reducer's broadcast, the reducer for their partials), so a
 // workgroup that cannot start until another one exits would hold everybody until the bounded waits expire.  256-thread
@@ -726,57 +751,17 @@ int enqueue_shard_direct(lam_hip_ctx *c, ShardBase &s, int k, double rel_error, 
         }
         // the fused update launch of iteration k-1 may have waited for the slices already (its waiter workgroup)
         const bool need_wait = P > 1 && k > 1 && s.waited_k != k - 1;
-        const bool timed = timed_iteration(c, s, k);
-        s.split_slot[slot] = hi > lo;
-        s.timed_slot[slot] = timed;
-        if (hi > lo) {
-            if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-            LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)s.Ap, nullptr, s.sc, 1, lo, hi));
-            if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-        }
-        if (need_wait) {
+        LAMCHK(launch_split_gemv<I>(c, s, k, slot, lo, hi, fa, [&]() -> int {
+            if (!need_wait) return 0;
             hipLaunchKernelGGL(wait_p_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const Mail *)s.mail, P, me, nb, seq - 1,
                                (const CgScalars *)s.sc, c->direct_err);
             LAUNCHED(c);
-        }
-        if (hi > lo) {
-            if (timed) RECORD(c, s.ev_g2[slot], s.stream);
-            LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)s.Ap, s.part_gemv, s.sc, 2, lo, hi, &fa));
-            if (timed) RECORD(c, s.ev_g3[slot], s.stream);
-        } else {
-            if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-            LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)s.Ap, s.part_gemv, s.sc, 0, 0, 0, &fa));
-            if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-        }
+            return 0;
+        }));
         // 2. x, r: waits in the kernel for the P partials of p.Ap; its reducer posts the r.r partial
         Finalize fb = fa;
         for (int q = 0; q < P; q++) fb.dst.p[q] = &c->peer_mail[q]->rr[me];
-        if (c->fuse_active) {
-            // steps 2 and 3 in ONE launch; without an own-slice panel (overlap 0) a waiter workgroup also holds the
-            // launch open until the peers' slices for the next GEMV are in: 2 launches per iteration
-            PtrList plf;
-            plf.n = P;
-            for (int q = 0; q < P; q++) plf.p[q] = c->peer_p[q];
-            MailPost postf = no_post();
-            postf.n = P; postf.rank = me; postf.seq = seq;
-            for (int q = 0; q < P; q++) postf.mail[q] = c->peer_mail[q];
-            static const char *dropf = getenv("LAM_HIP_DEBUG_DIRECT_DROP");
-            if (dropf && *dropf && atoi(dropf) == me && k == 3) postf.seq = ~0ull;      // test hook, see below
-            const bool waiter = P > 1 && !(hi > lo);
-            hipLaunchKernelGGL((update_fused_kernel<TV>), dim3(s.vec_blocks + 1 + (waiter ? 1 : 0)), dim3(kBlock), 0, s.stream,
-                               (const double *)nullptr, 0, s.sc, k, rel_error, (const TV *)s.p + s.row0, (const TV *)s.Ap, (TV *)s.x,
-                               (TV *)s.r, s.nrows, s.part_vec, s.vec_blocks, fb, MailWait{s.mail->pap, P, seq, c->direct_err},
-                               MailWait{s.mail->rr, P, seq, c->direct_err}, s.bcast, plf, s.row0, (volatile int *)s.host_flags, postf,
-                               (const Mail *)s.mail, nb);
-            LAUNCHED(c);
-            if (waiter) s.waited_k = k;
-            return 0;
-        }
-        hipLaunchKernelGGL((update_xr_kernel<TV>), dim3(s.vec_blocks + 1), dim3(kBlock), 0, s.stream, (const double *)nullptr, 0, s.sc, k,
-                           (const TV *)s.p + s.row0, (const TV *)s.Ap, (TV *)s.x, (TV *)s.r, s.nrows, s.part_vec, fb,
-                           MailWait{s.mail->pap, P, seq, c->direct_err});
-        LAUNCHED(c);
-        // 3. stop test + p slice into every replica + flags
+        // 3. stop test + p slice into every replica + flags (the fused launch's last part, or update_p): the peers' replicas and mailboxes
         PtrList pl;
         pl.n = P;
         for (int q = 0; q < P; q++) pl.p[q] = c->peer_p[q];
@@ -788,6 +773,23 @@ int enqueue_shard_direct(lam_hip_ctx *c, ShardBase &s, int k, double rel_error, 
         // ranks and the caller survives (tests/test_gpu_rank_mock.py).  Never set it otherwise.
         static const char *drop = getenv("LAM_HIP_DEBUG_DIRECT_DROP");
         if (drop && *drop && atoi(drop) == me && k == 3) post.seq = ~0ull;
+        if (c->fuse_active) {
+            // steps 2 and 3 in ONE launch; without an own-slice panel (overlap 0) a waiter workgroup also holds the
+            // launch open until the peers' slices for the next GEMV are in: 2 launches per iteration
+            const bool waiter = P > 1 && !(hi > lo);
+            hipLaunchKernelGGL((update_fused_kernel<TV>), dim3(s.vec_blocks + 1 + (waiter ? 1 : 0)), dim3(kBlock), 0, s.stream,
+                               (const double *)nullptr, 0, s.sc, k, rel_error, (const TV *)s.p + s.row0, (const TV *)s.Ap, (TV *)s.x,
+                               (TV *)s.r, s.nrows, s.part_vec, s.vec_blocks, fb, MailWait{s.mail->pap, P, seq, c->direct_err},
+                               MailWait{s.mail->rr, P, seq, c->direct_err}, s.bcast, pl, s.row0, (volatile int *)s.host_flags, post,
+                               (const Mail *)s.mail, nb);
+            LAUNCHED(c);
+            if (waiter) s.waited_k = k;
+            return 0;
+        }
+        hipLaunchKernelGGL((update_xr_kernel<TV>), dim3(s.vec_blocks + 1), dim3(kBlock), 0, s.stream, (const double *)nullptr, 0, s.sc, k,
+                           (const TV *)s.p + s.row0, (const TV *)s.Ap, (TV *)s.x, (TV *)s.r, s.nrows, s.part_vec, fb,
+                           MailWait{s.mail->pap, P, seq, c->direct_err});
+        LAUNCHED(c);
         hipLaunchKernelGGL((update_p_kernel<TV>), dim3(s.vec_blocks), dim3(kBlock), 0, s.stream, (const double *)nullptr, 0, s.sc, k,
                            rel_error, (const TV *)s.r, (const TV *)s.p + s.row0, pl, s.row0, s.nrows, (volatile int *)s.host_flags,
                            MailWait{s.mail->rr, P, seq, c->direct_err}, post);
@@ -867,16 +869,6 @@ int do_cg_init_exchange1_local(lam_hip_ctx *c)
     });
 }
 
-// One iteration on the gather-Ap exchange with several shards in one process (the reference's CPU path gathers Ap too,
-// ConjugateGradient_CPU_MPI_OMP.hpp:505; the single-process CUDA class gathers it on device 0,
-// ConjugateGradient_MultiGPUS_CUDA.cu:362-376).  Per shard: the GEMV stores every row of its Ap slice into its record in
-// EVERY shard's gather buffer (peer stores over xGMI) and its reducer workgroup does the same with the shard's p.Ap
-// partial; one event record.  Then the iteration's ONLY join -- through shard 0's stream (2(P-1)+1 runtime calls) or
-// all-to-all (P(P-1)) -- and the two full-length vector kernels, which need nothing from the peers any more: r.r is the
-// same sum on every shard.  Same kernels, same arithmetic as the rank mode's exchange 1: bit-identical to it.
-// The gather buffer is double (iteration parity): shard q may start GEMV k+1 -- which stores into its peers' buffers --
-// as soon as ITS update of iteration k is done, while a slower peer still reads the records of iteration k; GEMV k+2
-// cannot start before every peer has finished GEMV k+1, i.e. its update k.
 // Symmetric product on several shards (option "symmetric" on the gather-Ap exchange): the record a shard gathers is not its Ap
 // slice but its full-length CONTRIBUTION to A p (its rows' products over their cyclic half windows plus the mirrored products
 // for the columns it touched), followed by its part of p.Ap; the full-length vector step adds the P records in shard order.
@@ -892,6 +884,57 @@ int ensure_symv_gather(lam_hip_ctx *c, ShardBase &s)
     return 0;
 }
 
+// The product step of the gather-Ap exchange, for both topologies and both products: the one place that launches it, so one process
+// and the rank mode run the same kernels with the same arithmetic by construction.  `recs` names every place the shard's record (of
+// `stride` bytes) lives -- one process: its record in EVERY shard's gather buffer (peer stores over xGMI), rank mode: the one in
+// this rank's buffer, which the collective then gathers -- and recs.p[own] is the one in the shard's own buffer.  The record ends in
+// the shard's part of p.Ap (the tail, 8 bytes): the reducer workgroup of the launch leaves it there, a 1-block launch with option
+// "finalize" = 0.
+//   general product    the GEMV writes the Ap slice into the own record and into the peers' (ypeer);
+//   symmetric product  its second pass writes the shard's full-length contribution into all of them.
+// Timed as t_gemv: the product's launches; under "finalize" = 0 the reduction launch too for the symmetric product, not for the
+// general one (what the two products have always bracketed; kept as it is).
+template <typename I>
+int gather_ap_product(lam_hip_ctx *c, ShardBase &s, int k, int slot, const PtrList &recs, int own, uint64_t stride, bool sym)
+{
+    using TV = typename ImplTraits<I>::TV;
+    Finalize f = no_finalize(c);
+    f.active = c->opt_finalize ? 1 : 0;
+    f.slot = 0;
+    f.dst.n = recs.n;
+    for (int j = 0; j < recs.n; j++) f.dst.p[j] = (char *)recs.p[j] + stride - 8;
+    auto reduce = [&](int nparts) -> int {              // "finalize" = 0: the shard's part of p.Ap from its workgroups' partials
+        if (c->opt_finalize) return 0;
+        hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_gemv, nparts, f.dst, 0,
+                           (const CgScalars *)s.sc);
+        LAUNCHED(c);
+        return 0;
+    };
+    if (sym)
+        return timed_product(c, s, k, slot, false, [&]() -> int {
+            LAMCHK(I::launch_symv(c, s, (const TV *)s.p, nullptr, s.part_gemv, s.sc, &recs, &f));
+            return reduce(I::symv_reduce_grid(c->n));
+        });
+    PtrList ypeer;
+    ypeer.n = 0;
+    for (int j = 0; j < recs.n; j++)
+        if (j != own) ypeer.p[ypeer.n++] = recs.p[j];
+    LAMCHK(timed_product(c, s, k, slot, false, [&] {
+        return I::launch_gemv(c, s, (const TV *)s.p, (TV *)recs.p[own], s.part_gemv, s.sc, 0, 0, 0, &f, &ypeer);
+    }));
+    return reduce(s.gemv_blocks);
+}
+
+// One iteration on the gather-Ap exchange with several shards in one process (the reference's CPU path gathers Ap too,
+// ConjugateGradient_CPU_MPI_OMP.hpp:505; the single-process CUDA class gathers it on device 0,
+// ConjugateGradient_MultiGPUS_CUDA.cu:362-376).  Per shard: the product (gather_ap_product) stores the shard's record, its part of
+// p.Ap included, into EVERY shard's gather buffer; one event record.  Then the iteration's ONLY join -- through shard 0's stream
+// (2(P-1)+1 runtime calls) or all-to-all (P(P-1)) -- and the full-length vector step, which needs nothing from the peers any more:
+// r.r is the same sum on every shard.  The product and the vector step are the rank mode's (enqueue_iteration_exchange1): the
+// same launches from the same two functions, bit-identical to it.
+// The gather buffer is double (iteration parity): shard q may start GEMV k+1 -- which stores into its peers' buffers --
+// as soon as ITS update of iteration k is done, while a slower peer still reads the records of iteration k; GEMV k+2
+// cannot start before every peer has finished GEMV k+1, i.e. its update k.
 int enqueue_iteration_exchange1_local(lam_hip_ctx *c, int k, double rel_error, int slot)
 {
     return dispatch(c, [&](auto impl) -> int {
@@ -906,54 +949,10 @@ int enqueue_iteration_exchange1_local(lam_hip_ctx *c, int k, double rel_error, i
         };
         for (auto &s : c->sh) {
             LAMCHK(set_dev(c, s));
-            const uint64_t off = (uint64_t)s.index * stride;
-            if (sym) {
-                PtrList recs, tails;
-                recs.n = tails.n = P;
-                for (auto &t : c->sh) {
-                    recs.p[t.index] = buf(t) + off;
-                    tails.p[t.index] = buf(t) + off + stride - 8;
-                }
-                const bool timed = timed_iteration(c, s, k);
-                s.split_slot[slot] = false;
-                s.timed_slot[slot] = timed;
-                if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-                Finalize fs = no_finalize(c);
-                fs.active = c->opt_finalize ? 1 : 0;
-                fs.slot = 0;
-                fs.dst = tails;
-                LAMCHK(I::launch_symv(c, s, (const TV *)s.p, nullptr, s.part_gemv, s.sc, &recs, &fs));
-                if (!c->opt_finalize) {
-                    hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_gemv,
-                                       I::symv_reduce_grid(c->n), tails, 0, (const CgScalars *)s.sc);
-                    LAUNCHED(c);
-                }
-                if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-                LAMCHK(xt_begin(c, s, s.stream));
-                if (!(c->opt_join && &s == &c->sh[0])) RECORD(c, s.ev_a, s.stream);
-                continue;
-            }
-            Finalize f = no_finalize(c);
-            f.active = c->opt_finalize ? 1 : 0;
-            f.slot = 0;
-            f.dst.n = P;
-            PtrList yp;
-            yp.n = 0;
-            for (auto &t : c->sh) {
-                f.dst.p[t.index] = buf(t) + off + stride - 8;
-                if (&t != &s) yp.p[yp.n++] = buf(t) + off;
-            }
-            const bool timed = timed_iteration(c, s, k);
-            s.split_slot[slot] = false;
-            s.timed_slot[slot] = timed;
-            if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-            LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)(buf(s) + off), s.part_gemv, s.sc, 0, 0, 0, &f, &yp));
-            if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-            if (!c->opt_finalize) {
-                hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_gemv, s.gemv_blocks,
-                                   f.dst, 0, (const CgScalars *)s.sc);
-                LAUNCHED(c);
-            }
+            PtrList recs;
+            recs.n = P;
+            for (auto &t : c->sh) recs.p[t.index] = buf(t) + (uint64_t)s.index * stride;
+            LAMCHK(gather_ap_product<I>(c, s, k, slot, recs, s.index, stride, sym));
             LAMCHK(xt_begin(c, s, s.stream));
             if (!(c->opt_join && &s == &c->sh[0])) RECORD(c, s.ev_a, s.stream);
         }
@@ -1025,40 +1024,11 @@ int enqueue_iteration_exchange1(lam_hip_ctx *c, int k, double rel_error, int slo
         const uint64_t stride = sym ? c->symv_stride_bytes() : c->ex1_stride_bytes(), base = c->ex1_base();
         char *const gathered = sym ? (char *)s.symv_gather : (char *)s.ap_gather;
         char *rec = gathered + (uint64_t)c->rank * stride;
-        // 1. GEMV straight into this rank's record; its last workgroup leaves the rank's p.Ap partial
-        //    behind the slice (with option "finalize" = 0: a 1-block launch does)
-        Finalize f = no_finalize(c);
-        f.active = c->opt_finalize ? 1 : 0;
-        f.dst.n = 1; f.dst.p[0] = rec + stride - 8; f.slot = 0;
-        const bool timed = timed_iteration(c, s, k);
-        s.split_slot[slot] = false;
-        s.timed_slot[slot] = timed;
-        if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-        if (sym) {
-            // the symmetric product's two passes leave this rank's full-length contribution and its p.Ap part in its record
-            PtrList recs, tails;
-            recs.n = tails.n = 1;
-            recs.p[0] = rec;
-            tails.p[0] = rec + stride - 8;
-            Finalize fs = no_finalize(c);
-            fs.active = c->opt_finalize ? 1 : 0;
-            fs.slot = 0;
-            fs.dst = tails;
-            LAMCHK(I::launch_symv(c, s, (const TV *)s.p, nullptr, s.part_gemv, s.sc, &recs, &fs));
-            if (!c->opt_finalize) {
-                hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_gemv,
-                                   I::symv_reduce_grid(c->n), tails, 0, (const CgScalars *)s.sc);
-                LAUNCHED(c);
-            }
-        } else {
-        LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)rec, s.part_gemv, s.sc, 0, 0, 0, &f));
-        }
-        if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-        if (!sym && !c->opt_finalize) {
-            hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, s.stream, (const double *)s.part_gemv, s.gemv_blocks,
-                               f.dst, 0, (const CgScalars *)s.sc);
-            LAUNCHED(c);
-        }
+        // 1. the product straight into this rank's record, the rank's part of p.Ap behind it
+        PtrList recs;
+        recs.n = 1;
+        recs.p[0] = rec;
+        LAMCHK(gather_ap_product<I>(c, s, k, slot, recs, 0, stride, sym));
         // 2. the iteration's only collective
         LAMCHK(xt_begin(c, s, s.stream));
         NCCLCHK(c, ncclAllGather(rec, gathered, stride, ncclChar, c->comm, s.stream));

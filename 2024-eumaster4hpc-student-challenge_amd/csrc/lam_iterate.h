@@ -158,44 +158,25 @@ int do_cg_init(lam_hip_ctx *c)
 // what the next phase's stream waits refer to).  One host thread: phase by phase over all shards.  One host thread
 // per shard (option "host_threads", the shape of the reference's OpenMP-thread-per-device loop,
 // ConjugateGradient_MultiGPUS_CUDA.cu:337-378): a host barrier between the phases (iterate_threaded).
-//   A  GEMV (+ partial p.Ap) and its post             B  wait for the peers' p.Ap; x, r update (+ partial r.r); post
+//   A  GEMV (+ partial p.Ap; the product step's helpers are lam_exchange.h's) and its post
+//   B  wait for the peers' p.Ap; x, r update (+ partial r.r); post
 //   C  wait for the peers' r.r; stop test + p update into every replica; post        D  wait for the peers' p slices
 template <typename I>
 int phase_gemv(lam_hip_ctx *c, ShardBase &s, int k, int slot)
 {
     using TV = typename ImplTraits<I>::TV;
-    // With an own-slice panel: that panel first (it only needs the p slice this shard wrote itself), then wait for
-    // the all-gather, then the remaining columns.
-    uint64_t lo, hi;
-    cg_panel<I>(c, s, &lo, &hi);
-    const bool timed = timed_iteration(c, s, k);
-    s.timed_slot[slot] = timed;
-    const bool fin_a = producer_reduces(c, false);
     if (c->symv_active()) {
-        s.split_slot[slot] = false;
-        if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-        LAMCHK(I::launch_symv(c, s, (const TV *)s.p, (TV *)s.Ap, s.part_gemv, s.sc));
-        if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-        return reduce_post(c, s, false, true, true, fin_a);
-    }
-    s.split_slot[slot] = hi > lo;
-    const Finalize fa = make_finalize(c, s, false);
-    if (hi > lo) {
-        // the two panels are timed separately so that t_gemv is kernel time, not the wait in between
-        if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-        LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)s.Ap, nullptr, s.sc, 1, lo, hi));
-        if (timed) RECORD(c, s.ev_g1[slot], s.stream);
-        if (c->gather_pending) WAITEV(c, s.stream, s.ev_gathered);
-        if (timed) RECORD(c, s.ev_g2[slot], s.stream);
-        LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)s.Ap, s.part_gemv, s.sc, 2, lo, hi, &fa));
-        if (timed) RECORD(c, s.ev_g3[slot], s.stream);
+        LAMCHK(timed_product(c, s, k, slot, false, [&] { return I::launch_symv(c, s, (const TV *)s.p, (TV *)s.Ap, s.part_gemv, s.sc); }));
     } else {
-        if (c->gather_pending) WAITEV(c, s.stream, s.ev_gathered);
-        if (timed) RECORD(c, s.ev_g0[slot], s.stream);
-        LAMCHK(I::launch_gemv(c, s, (const TV *)s.p, (TV *)s.Ap, s.part_gemv, s.sc, 0, 0, 0, &fa));
-        if (timed) RECORD(c, s.ev_g1[slot], s.stream);
+        // with an own-slice panel the wait for the all-gather of p comes behind that panel (launch_split_gemv)
+        uint64_t lo, hi;
+        cg_panel<I>(c, s, &lo, &hi);
+        LAMCHK(launch_split_gemv<I>(c, s, k, slot, lo, hi, make_finalize(c, s, false), [&]() -> int {
+            if (c->gather_pending) WAITEV(c, s.stream, s.ev_gathered);
+            return 0;
+        }));
     }
-    return reduce_post(c, s, false, true, true, fin_a);
+    return reduce_post(c, s, false, true, true, producer_reduces(c, false));
 }
 
 template <typename I>

@@ -1,8 +1,22 @@
-// lam_launch.h -- typed kernel launchers (Impl<TA,TV>: GEMV shapes, symmetric product), dtype dispatch, shard resources.
+// lam_launch.h -- the blank Finalize (no_finalize), typed kernel launchers (Impl<TA,TV>: GEMV shapes, symmetric product), dtype dispatch, shard resources.
 // Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 #pragma once
 
 namespace {
+
+// "no in-kernel reduction" (lam_kernels.h, Finalize): what a launch without a reducer workgroup carries, and the blank every other
+// Finalize starts from
+Finalize no_finalize(const lam_hip_ctx *c)
+{
+    Finalize f;
+    f.active = 0;
+    f.mail = 0;
+    f.seq = 0;
+    f.dst.n = 0;
+    f.slot = 0;
+    f.host_err = c ? c->direct_err : nullptr;
+    return f;
+}
 
 // ---- typed implementation ----------------------------------------------------------------------
 // (the symmetric product's plan -- SymvPlan, symv_plan -- is host-only arithmetic: lam_host_plan.h)
@@ -177,8 +191,7 @@ struct Impl {
         PtrList none;
         none.n = 0;
         const PtrList &d = dst ? *dst : none;
-        Finalize off;
-        off.active = 0; off.mail = 0; off.seq = 0; off.dst.n = 0; off.slot = 0; off.host_err = c->direct_err;
+        const Finalize off = no_finalize(c);
         const Finalize &f = fin ? *fin : off;
         return symv_nv(c) == 2 ? launch_symv_nv<2>(c, s, p, y, partial, sc, d, f) : launch_symv_nv<1>(c, s, p, y, partial, sc, d, f);
     }
@@ -203,8 +216,7 @@ struct Impl {
         for (auto &yp : a.ypeer) yp = nullptr;
         if (ypeers != nullptr)
             for (int j = 0; j < ypeers->n && a.n_ypeer < kMaxShards - 1; j++) a.ypeer[a.n_ypeer++] = (TV *)ypeers->p[j];
-        if (fin != nullptr && partial != nullptr) a.fin = *fin;
-        else { a.fin.active = 0; a.fin.mail = 0; a.fin.seq = 0; a.fin.dst.n = 0; a.fin.slot = 0; a.fin.host_err = c->direct_err; }
+        a.fin = (fin != nullptr && partial != nullptr) ? *fin : no_finalize(c);
         a.nrows = s.nrows; a.n = c->n; a.row0 = s.row0; a.lda = c->lda;
         // the vector kernels cover whole 16-byte vectors: for an N that is not a multiple of the vector width the last one
         // reaches into the (zero) padding of the row and behind the end of p (zero too: set_problem)

@@ -145,9 +145,18 @@ def exact_first_step(dtype_name, n):
         assert abs(s.stats["rel_err"] - re_host) <= bound, (s.stats["rel_err"], re_host, bound)
 
 
+def call_counts():
+    """The runtime calls of cg_init + 11 iterations on the gather-Ap exchange with finalize = 0 (three shards, one rank through RCCL):
+    one JSON line, compared with the literals of tests/test_gpu_iteration_call_counts.py by the test that started this process."""
+    import json
+    import test_gpu_iteration_call_counts as T
+    print(json.dumps({f"{case}/timing{timing}": T.measure(lam, n, shards, options, timing)
+                      for case, (n, shards, options) in T.TUNING_CASES.items() for timing in (1, 8)}))
+
+
 CASES = {"mfma": (mfma, (int, int)), "launch_chain": (launch_chain, (str, int, int)), "host_enqueue": (host_enqueue, (int, int)),
          "persistent": (persistent, (str, int)), "exact_gemv": (exact_gemv, (str, int)),
-         "exact_first_step": (exact_first_step, (str, int))}
+         "exact_first_step": (exact_first_step, (str, int)), "call_counts": (call_counts, ())}
 
 
 def main():
