@@ -128,6 +128,15 @@ struct MultiState {
     bool shifted = false;
     MshiftState ms;
     MinresState mr;
+    // symmetric batched product (option "symmetric_many", multi_sym_ensure): the batch's own plan and partials, nothing shared with
+    // ShardBase::symv_*.  The plan is built at first use for the batch's n and the storage's vector width (sym_vec); the partials are
+    // K-wide records and grow-only in K (sym_cap_K); released with the batch.
+    SymvTask *sym_tasks = nullptr;
+    uint32_t *sym_index = nullptr;
+    SymvIndex sym_ix = {};
+    int sym_ntasks = 0, sym_vec = 0, sym_cap_K = 0;
+    uint64_t sym_rowpart_elems = 0;      // per column
+    void *sym_rowpart = nullptr, *sym_colpart = nullptr;
 };
 
 // Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,
@@ -181,6 +190,8 @@ struct lam_hip_ctx {
     int64_t opt_overlap = 1;       // rank mode: all-gather on its own stream under the own-slice GEMV panel
     int64_t opt_panel_lo = 0, opt_panel_hi = 0;  // testing: split the CG GEMV into [lo,hi) + the rest
     bool gather_pending = false;   // an all-gather of p is in flight on comm_stream
+    int64_t opt_symmetric_many = 0;   // the batched product (K <= 4) reads only the upper triangle: 0 never, 1 where it pays, 2 always
+    bool symv_many_effective = false; // the last batched product launch ran the symmetric kernels
     int64_t opt_symmetric = 0;     // single shard: read only the upper triangle (caller asserts A == A^T)
     int64_t opt_exchange = 0;      // 0 = sliced vectors, three exchanges per iteration (p.Ap, r.r, p slices); 1 = gather-Ap: ONE
                                    // exchange of [Ap slice | p.Ap partial] per iteration, r and p full-length on every shard;

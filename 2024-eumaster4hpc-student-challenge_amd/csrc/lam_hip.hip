@@ -1125,6 +1125,13 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
         c->sym_refused = false;
         c->cg_ready = false;        // other kernels, other partial arrays
     }
+    else if (!strcmp(name, "symmetric_many")) {
+        // the batched product's own switch; as with "symmetric" the caller vouches for A = A^T (lam_hip_check_symmetry measures it)
+        if (value < 0 || value > 2)
+            return fail(c, LAM_HIP_EINVAL, "symmetric_many = %lld: 0 (general batched product), 1 (symmetric where it pays) or 2 (always, K <= 4)",
+                        (long long)value);
+        c->opt_symmetric_many = value;
+    }
     else if (!strcmp(name, "gemv_timing")) c->opt_gemv_timing = value < 0 ? 0 : value;
     else if (!strcmp(name, "verify_direct")) c->opt_verify_direct = value;
     else if (!strcmp(name, "host_threads") || !strcmp(name, "exchange_hub")) {
@@ -1186,6 +1193,8 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "hip_calls_wait")) *value = (int64_t)c->n_wait.load();
     else if (!strcmp(name, "hip_calls_setdevice")) *value = (int64_t)c->n_setdev.load();
     else if (!strcmp(name, "symmetric")) *value = c->opt_symmetric;
+    else if (!strcmp(name, "symmetric_many")) *value = c->opt_symmetric_many;
+    else if (!strcmp(name, "symmetric_many_effective")) *value = c->symv_many_effective ? 1 : 0;
     else if (!strcmp(name, "symmetric_effective")) *value = (c->symv_active() || c->symv_multi_active()) ? 1 : 0;
     else if (!strcmp(name, "exchange_effective")) *value = c->cg_direct ? 2 : ((c->exchange1_ok() && !c->exchange2_wanted()) ? 1 : 0);
     else if (!strcmp(name, "panel_lo")) *value = c->opt_panel_lo;

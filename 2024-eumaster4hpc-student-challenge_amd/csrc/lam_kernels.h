@@ -31,7 +31,7 @@
 //     accumulate, which is how the rank mode overlaps the all-gather of p with its own-slice panel.
 //   * the *_full_kernel family implements the single-exchange iteration (gather of Ap, full-length r and p on every shard);
 //     symv_*_kernel implement the opt-in symmetric product (every pair {i, j} read once: the upper triangle on one shard,
-//     cyclic half windows on several row shards).
+//     cyclic half windows on several row shards); symv_many_*_kernel are its K-wide form for the batch (option "symmetric_many").
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -2615,6 +2615,271 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
 #pragma unroll
             for (int r = 1; r < R; r++) t += s_dot[r * K + tid];
             a.partial[(size_t)tid * gridDim.x + blockIdx.x] = t;
+        }
+    }
+}
+
+// Symmetric batched product (option "symmetric_many", lam_multi.h multi_launch_gemv): Y = A P for K = 1, 2, 4 interleaved columns
+// reading every pair {A_ij, A_ji} once -- the two passes of the single symmetric product ("Symmetric product" above: one shard, the
+// upper triangle, NV = 1, the plan of symv_plan unchanged) with K of everything a lane keeps per column of P: its p values, its column
+// partials, its 8 row partials.  The matrix loads, the tasks, the lean / masked / ragged loops and the use rule are the single path's;
+// so is, statement for statement, the order of every sum of column j: column j of Y is bit for bit what symv_task_kernel +
+// symv_reduce_kernel give for that vector alone, whatever K is and whatever the other columns hold.
+// Partials are K-wide records: rowpart[(rp + row) * K + j], colpart[(task * SS + column) * K + j] (64-bit offsets: the products with K
+// pass 2^32).  The LDS row buffer is K-wide too (fp64 K = 4: 32 KiB); the idle dynamic LDS behind it keeps the launch at three
+// workgroups per CU as in the single path.
+constexpr int kSymvManyMaxK = 4;       // K = 8 stays on the general product (staging- and barrier-bound, not byte-bound: DESIGN §8)
+template <typename T> struct ShiftArg { T s[kSymvManyMaxK]; };       // SHIFT only: s_j of Y_j = (A + s_j I) P_j, by value
+template <typename T, int K> constexpr unsigned symv_many_lds_pad() { return kSymvLdsPerWorkgroup - (unsigned)sizeof(T) * kWaves * kSymvRowsLds * K; }
+template <typename TA, typename T, int K>
+__global__ void __launch_bounds__(kBlock)
+symv_many_task_kernel(const TA *__restrict__ A, const T *__restrict__ p, const SymvTask *__restrict__ tasks, T *__restrict__ rowpart,
+                      T *__restrict__ colpart, uint64_t lda, uint64_t ncols_vec, uint64_t n, const MultiScalars *sc)
+{
+    using MV = MatVec<TA>;
+    using vec_t = typename MV::vec_t;
+    constexpr int VEC = MV::N, SS = kBlock * VEC;
+    typedef T tvec_t __attribute__((ext_vector_type(VEC)));          // 16 bytes of a K-wide record run: flat element f = i * K + j
+    static_assert(sizeof(T) == sizeof(TA), "fp64 / fp32 storage: a 16-byte vector holds VEC elements of either");
+    __shared__ T s_rows[kWaves][kSymvRowsLds * K];
+    if (sc != nullptr && sc->all_stop) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    SymvTask t = tasks[blockIdx.x];
+    const bool interior = (t.nrows & kSymvInterior) != 0, full = (t.nrows & kSymvFull) != 0;
+    t.nrows &= ~kSymvFlags;
+    const uint64_t c0 = (uint64_t)t.strip * SS, c = c0 + (uint64_t)tid * VEC;       // this lane's columns: c + i
+    const uint64_t grow0 = t.row0;
+    const bool live = c < ncols_vec;
+    T pc[K][VEC], cacc[K][VEC];
+    {
+        tvec_t in[K];
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+#pragma unroll
+            for (int i = 0; i < VEC; i++) in[q][i] = (T)0;
+            if (live) in[q] = *reinterpret_cast<const tvec_t *>(p + c * K + (uint64_t)q * VEC);
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++)
+#pragma unroll
+            for (int i = 0; i < VEC; i++) { pc[j][i] = in[(i * K + j) / VEC][(i * K + j) % VEC]; cacc[j][i] = (T)0; }
+    }
+    // the row partials of the last (up to) 256 rows, ending at row `end` of the task: out of LDS into rowpart, K-wide records
+    auto flush_rows = [&](uint32_t end) {
+        const uint32_t beg = (end - 1) & ~(uint32_t)(kSymvRowsLds - 1);
+        const uint32_t stop = end < t.nrows ? end : t.nrows;
+        __syncthreads();
+        for (uint32_t e = beg * K + tid; e < stop * K; e += kBlock) {
+            const uint32_t q = e - beg * K;
+            __builtin_nontemporal_store((s_rows[0][q] + s_rows[1][q]) + (s_rows[2][q] + s_rows[3][q]), rowpart + (uint64_t)t.rp * K + e);
+        }
+        __syncthreads();
+    };
+    // one 8-row step's tail: per column the wave's row totals, parked in LDS
+    auto park = [&](const T (&racc)[K][8], uint32_t b) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const T tot = wave_sum8(racc[j]);
+            if ((lane & 7) == 0) s_rows[wave][((b & (kSymvRowsLds - 1)) + (lane >> 3)) * K + j] = tot;
+        }
+        if (((b + 8) & (kSymvRowsLds - 1)) == 0 || b + 8 >= t.nrows) flush_rows(b + 8);
+    };
+    auto lean_loop = [&](auto masked_tag) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        const TA *rows = A + (uint64_t)t.row0 * lda + c0;          // uniform
+        const T *prow = p + grow0 * K;
+        vec_t a0[4], a1[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            a0[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(rows + (uint64_t)k * lda) + tid);
+            a1[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(rows + (uint64_t)(k + 4) * lda) + tid);
+        }
+        for (uint32_t b = 0; b < t.nrows; b += 8, prow += 8 * K) {
+            rows += 8 * lda;
+            const bool more = b + 8 < t.nrows;
+            T racc[K][8];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    const T pr = prow[k * K + j];
+                    T r = (T)0;
+#pragma unroll
+                    for (int i = 0; i < VEC; i++) {
+                        bool rs = true, cs = true;
+                        if (MASKED) symv_use<false>(c + i, grow0 + b + k, n, &rs, &cs);
+                        if (rs) r = fma_tv((T)MV::get(a0[k], i), pc[j][i], r);
+                        if (cs) cacc[j][i] = fma_tv((T)MV::get(a0[k], i), pr, cacc[j][i]);
+                    }
+                    racc[j][k] = r;
+                }
+            if (more) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) a0[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(rows + (uint64_t)k * lda) + tid);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    const T pr = prow[(4 + k) * K + j];
+                    T r = (T)0;
+#pragma unroll
+                    for (int i = 0; i < VEC; i++) {
+                        bool rs = true, cs = true;
+                        if (MASKED) symv_use<false>(c + i, grow0 + b + 4 + k, n, &rs, &cs);
+                        if (rs) r = fma_tv((T)MV::get(a1[k], i), pc[j][i], r);
+                        if (cs) cacc[j][i] = fma_tv((T)MV::get(a1[k], i), pr, cacc[j][i]);
+                    }
+                    racc[j][4 + k] = r;
+                }
+            if (more) {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    a1[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(rows + (uint64_t)(k + 4) * lda) + tid);
+            }
+            park(racc, b);
+        }
+    };
+    if (interior) lean_loop(std::false_type());
+    else if (full) lean_loop(std::true_type());
+    else {
+        // ragged strips and row runs: every load and every product tested
+        const TA *Arow = A + (uint64_t)t.row0 * lda + c;
+        for (uint32_t b = 0; b < t.nrows; b += 8) {
+            vec_t a[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+#pragma unroll
+                for (int i = 0; i < VEC; i++) a[k][i] = 0;
+                // a vector whose columns all lie left of the diagonal is not read at all
+                if (live && b + k < t.nrows && c + VEC > grow0 + b + k)
+                    a[k] = __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(Arow + (uint64_t)(b + k) * lda));
+            }
+            T racc[K][8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint64_t grow = grow0 + b + k;
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    const T pr = b + k < t.nrows ? p[grow * K + j] : (T)0;
+                    T r = (T)0;
+#pragma unroll
+                    for (int i = 0; i < VEC; i++) {
+                        bool rs, cs;
+                        symv_use<false>(c + i, grow, n, &rs, &cs);
+                        if (rs) r = fma_tv((T)MV::get(a[k], i), pc[j][i], r);
+                        if (cs) cacc[j][i] = fma_tv((T)MV::get(a[k], i), pr, cacc[j][i]);
+                    }
+                    racc[j][k] = r;
+                }
+            }
+            park(racc, b);
+        }
+    }
+    if (live) {
+        T *dst = colpart + ((uint64_t)blockIdx.x * SS + (uint64_t)tid * VEC) * K;
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+            tvec_t out;
+#pragma unroll
+            for (int f = 0; f < VEC; f++) out[f] = cacc[(q * VEC + f) % K][(q * VEC + f) / K];
+            __builtin_nontemporal_store(out, reinterpret_cast<tvec_t *>(dst) + q);
+        }
+    }
+}
+
+// Second pass of the symmetric batched product: symv_reduce_kernel (one shard) with K accumulators per thread -- 32 rows per
+// workgroup, the same fixed order of the row-run terms and of the strip's task list for every column.  The epilogue has one thread per
+// (row, column), as multi_gemv_kernel's: SHIFT adds s_j p_j[row] with one fma, y[row * K + j] is stored, and the workgroup's
+// p_j.(A p_j) partial goes to partial[j * gridDim.x + block] (gridDim.x = ceil(n / 32): what the batch's consumers are told).
+template <typename T, int SS, int K, bool SHIFT>
+__global__ void __launch_bounds__(kBlock)
+symv_many_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart, const uint32_t *__restrict__ index, SymvIndex ix,
+                        const T *__restrict__ p, T *__restrict__ y, double *__restrict__ partial, uint64_t n, ShiftArg<T> shift,
+                        const MultiScalars *sc)
+{
+    constexpr int RB = kSymvReduceRows, G = kBlock / RB;
+    static_assert(RB * K <= kBlock, "one epilogue thread per (row, column)");
+    __shared__ T s[G][RB * K];
+    __shared__ double s_dot[K][RB];
+    __shared__ uint32_t s_list[kSymvListChunk];
+    if (sc != nullptr && sc->all_stop) return;
+    const int l = threadIdx.x % RB, g = threadIdx.x / RB;
+    const uint64_t i = (uint64_t)blockIdx.x * RB + l;
+    T acc[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = (T)0;
+    if (i < n) {
+        const uint32_t *run = index + ix.runs + 5 * index[ix.row8 + (i >> 3)];
+        const uint32_t cnt = run[1], h = run[3];
+        const T *src = rowpart + ((uint64_t)run[4] + (i - run[2])) * K;
+        const uint64_t hk = (uint64_t)h * K;
+        uint32_t q = g;
+        for (; q + 3 * G < cnt; q += 4 * G) {
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const T a0 = src[(uint64_t)q * hk + j], a1 = src[(uint64_t)(q + G) * hk + j];
+                const T a2 = src[(uint64_t)(q + 2 * G) * hk + j], a3 = src[(uint64_t)(q + 3 * G) * hk + j];
+                acc[j] += (a0 + a1) + (a2 + a3);
+            }
+        }
+        for (; q < cnt; q += G)
+#pragma unroll
+            for (int j = 0; j < K; j++) acc[j] += src[(uint64_t)q * hk + j];
+    }
+    {
+        const uint32_t s0 = (uint32_t)(((uint64_t)blockIdx.x * RB) / SS);
+        const uint32_t lb = index[ix.strip_base + s0], le = index[ix.strip_base + s0 + 1];
+        const uint32_t *list = index + ix.strip_tasks;
+        const T *src = colpart + (i - (uint64_t)s0 * SS) * K;
+        constexpr uint64_t SK = (uint64_t)SS * K;
+        for (uint32_t base = lb; base < le; base += kSymvListChunk) {
+            const uint32_t cnt = le - base < (uint32_t)kSymvListChunk ? le - base : (uint32_t)kSymvListChunk;
+            __syncthreads();                                  // the previous chunk has been consumed
+            for (uint32_t q = threadIdx.x; q < cnt; q += kBlock) s_list[q] = list[base + q];
+            __syncthreads();
+            if (i < n) {
+                uint32_t k = g;
+                for (; k + 7 * G < cnt; k += 8 * G) {
+#pragma unroll
+                    for (int j = 0; j < K; j++) {
+                        T a[8];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) a[u] = src[(uint64_t)s_list[k + u * G] * SK + j];
+                        acc[j] += ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+                    }
+                }
+                for (; k < cnt; k += G)
+#pragma unroll
+                    for (int j = 0; j < K; j++) acc[j] += src[(uint64_t)s_list[k] * SK + j];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) s[g][l * K + j] = acc[j];
+    __syncthreads();
+    if (threadIdx.x < RB * K) {
+        const int e = threadIdx.x, row = e / K, j = e % K;
+        const uint64_t ir = (uint64_t)blockIdx.x * RB + row;
+        T t = s[0][e];
+#pragma unroll
+        for (int k = 1; k < G; k++) t += s[k][e];
+        double d = 0.0;
+        if (ir < n) {
+            const T pj = p[ir * K + j];
+            if constexpr (SHIFT) t = fma_tv(shift.s[j], pj, t);
+            y[ir * K + j] = t;
+            d = (double)t * (double)pj;
+        }
+        s_dot[j][row] = d;
+    }
+    if (partial != nullptr) {
+        __syncthreads();
+        if (threadIdx.x < K) {
+            double d = 0.0;
+#pragma unroll
+            for (int k = 0; k < RB; k++) d += s_dot[threadIdx.x][k];
+            partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = d;
         }
     }
 }

@@ -24,6 +24,8 @@
 // Shifts (column j is the system (A + s_j I) x_j = b_j) travel by value in the product's arguments: its SHIFT = true instantiation, and
 // under Jacobi the DK = true vector kernels on a K-wide dinv_k = 1 / (A_ii + s_j).  No shifts, or all of them zero: the plain ones.
 // Only MINRES takes a negative shift and can leave one in force; CG refuses to run under it.
+// Option "symmetric_many" (K <= 4): the product launch becomes the two passes of the symmetric batched product (multi_sym_launch: every
+// pair {A_ij, A_ji} read once, one more launch per product, its own plan and partials in MultiState); K = 8 and option 0 are untouched.
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
@@ -58,6 +60,7 @@ void multi_release(lam_hip_ctx *c)
     free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.part_rr, m.res, m.sc});
     free_dev({m.ms.XS, m.ms.PS, m.ms.sc});
     free_dev({m.mr.W, m.mr.WOLD, m.mr.sc});
+    free_dev({m.sym_tasks, m.sym_index, m.sym_rowpart, m.sym_colpart});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -227,12 +230,123 @@ int mshift_dispatch(lam_hip_ctx *c, F &&f)
     return fail(c, LAM_HIP_EINVAL, "the multi-shift path has no kernels for dtype %d", c->dtype);
 }
 
+// ---- symmetric batched product (option "symmetric_many"; kernels: lam_kernels.h, "Symmetric batched product") ---------------
+// Value 1 ("where it pays") admits the (dtype, K) whose symmetric batched iteration measured faster than the general one of the same
+// build at its size, by more than the spread between the windows of the two figures (tools/symv_many_probe.py,
+// profiles/symv_many_probe.txt; symmetric / general per iteration): fp64 N = 65536  K = 1: 0.53, 2: 0.50, 4: 0.53;
+// fp32 N = 131072  K = 1: 0.52, 2: 0.53, 4: 0.50.  All six are admitted; a (dtype, K) that lost would read false here and stay
+// reachable through value 2.
+bool multi_sym_admitted(const lam_hip_ctx *c, int K)
+{
+    static constexpr bool admitted[2][kSymvManyMaxK + 1] = {/* fp64: K = - 1 2 - 4 */ {false, true, true, false, true},
+                                                            /* fp32 */ {false, true, true, false, true}};
+    if (K < 1 || K > kSymvManyMaxK) return false;
+    return c->dtype == LAM_HIP_F64 ? admitted[0][K] : (c->dtype == LAM_HIP_F32 ? admitted[1][K] : false);
+}
+bool multi_sym_wanted(const lam_hip_ctx *c, int K)
+{
+    if (K > kSymvManyMaxK || c->n == 0) return false;
+    if (c->opt_symmetric_many >= 2) return true;
+    return c->opt_symmetric_many == 1 && c->n * c->n * (uint64_t)c->esz_a() >= (192ull << 20) && multi_sym_admitted(c, K);
+}
+int multi_sym_grid(const lam_hip_ctx *c) { return (int)((c->n + kSymvReduceRows - 1) / kSymvReduceRows); }
+// p.Ap partials per column of the product multi_launch_gemv runs for instantiation K: what its consumers are told
+int multi_product_blocks(const lam_hip_ctx *c, int K) { return multi_sym_wanted(c, K) ? multi_sym_grid(c) : multi_gemv_grid(c); }
+
+void multi_sym_release(MultiState &m)
+{
+    free_dev({m.sym_tasks, m.sym_index, m.sym_rowpart, m.sym_colpart});
+    m.sym_tasks = nullptr; m.sym_index = nullptr; m.sym_rowpart = m.sym_colpart = nullptr;
+    m.sym_ntasks = m.sym_vec = m.sym_cap_K = 0;
+    m.sym_rowpart_elems = 0;
+}
+
+// Plan (symv_plan as the single product has it: one shard, strips of 256 * VEC columns) at first use for the batch's n; partials for K
+// columns, grow-only.  All of a step or none of it: a failed allocation leaves what there was, and the batch runs on under option 0.
+template <typename TA, typename TV>
+int multi_sym_ensure(lam_hip_ctx *c, int K)
+{
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    constexpr int VEC = MatVec<TA>::N;
+    constexpr uint64_t SS = (uint64_t)kBlock * VEC;
+    if (m.sym_tasks != nullptr && m.sym_vec != VEC) {        // the same n under another storage type: another plan
+        HIPCHK(c, hipStreamSynchronize(s.stream));
+        multi_sym_release(m);
+    }
+    if (m.sym_tasks == nullptr) {
+        SymvPlan plan;
+        symv_plan(c->n, c->ncols_vec(), SS, 0, c->n, false, &plan);
+        if (plan.tasks.empty()) return fail(c, LAM_HIP_EINVAL, "symmetric batched product: no tasks");
+        if (plan.rowpart_elems >> 32) return fail(c, LAM_HIP_EINVAL, "symmetric batched product: too many row partials for 32-bit offsets");
+        DevBuf t, sb;
+        HIPCHK(c, hipMalloc(&t.p, plan.tasks.size() * sizeof(SymvTask)));
+        HIPCHK(c, hipMalloc(&sb.p, plan.index.size() * sizeof(uint32_t)));
+        HIPCHK(c, hipMemcpy(t.p, plan.tasks.data(), plan.tasks.size() * sizeof(SymvTask), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(sb.p, plan.index.data(), plan.index.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        m.sym_tasks = t.as<SymvTask>(); m.sym_index = sb.as<uint32_t>();
+        t.p = sb.p = nullptr;
+        m.sym_ix = plan.ix;
+        m.sym_ntasks = (int)plan.tasks.size();
+        m.sym_rowpart_elems = plan.rowpart_elems;
+        m.sym_vec = VEC;
+        m.sym_cap_K = 0;             // (no partials yet: multi_sym_release has run, or nothing was ever allocated)
+    }
+    if (K > m.sym_cap_K) {
+        const size_t rbytes = (size_t)m.sym_rowpart_elems * K * sizeof(TV), cbytes = (size_t)m.sym_ntasks * SS * K * sizeof(TV);
+        DevBuf rp, cp;
+        HIPCHK(c, hipMalloc(&rp.p, rbytes));
+        HIPCHK(c, hipMalloc(&cp.p, cbytes));
+        // columns behind the end of a ragged strip are never written by a task: the second pass does not read them either
+        HIPCHK(c, hipMemsetAsync(cp.p, 0, cbytes, s.stream));
+        HIPCHK(c, hipStreamSynchronize(s.stream));           // and no launch on the smaller buffers is in flight
+        free_dev({m.sym_rowpart, m.sym_colpart});
+        m.sym_rowpart = rp.p; m.sym_colpart = cp.p;
+        rp.p = cp.p = nullptr;
+        m.sym_cap_K = K;
+    }
+    return 0;
+}
+
+template <typename TA, typename TV, int K>
+int multi_sym_launch(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const MultiScalars *sc, const double *shift)
+{
+    MultiState &m = c->multi;
+    ShardBase &s = c->sh[0];
+    c->symv_many_effective = false;
+    LAMCHK((multi_sym_ensure<TA, TV>(c, K)));
+    constexpr int SS = kBlock * MatVec<TA>::N;
+    constexpr unsigned lds_pad = symv_many_lds_pad<TV, K>();
+    hipLaunchKernelGGL((symv_many_task_kernel<TA, TV, K>), dim3(m.sym_ntasks), dim3(kBlock), lds_pad, s.stream,
+                       (const TA *)s.A, P, (const SymvTask *)m.sym_tasks, (TV *)m.sym_rowpart, (TV *)m.sym_colpart, c->lda, c->ncols_vec(),
+                       c->n, sc);
+    LAUNCHED(c);
+    ShiftArg<TV> sa;
+    for (int j = 0; j < kSymvManyMaxK; j++) sa.s[j] = shift ? (TV)shift[j] : (TV)0;
+    if (shift)
+        hipLaunchKernelGGL((symv_many_reduce_kernel<TV, SS, K, true>), dim3(multi_sym_grid(c)), dim3(kBlock), 0, s.stream,
+                           (const TV *)m.sym_rowpart, (const TV *)m.sym_colpart, (const uint32_t *)m.sym_index, m.sym_ix, P, Y, partial, c->n,
+                           sa, sc);
+    else
+        hipLaunchKernelGGL((symv_many_reduce_kernel<TV, SS, K, false>), dim3(multi_sym_grid(c)), dim3(kBlock), 0, s.stream,
+                           (const TV *)m.sym_rowpart, (const TV *)m.sym_colpart, (const uint32_t *)m.sym_index, m.sym_ix, P, Y, partial, c->n,
+                           sa, sc);
+    LAUNCHED(c);
+    c->symv_many_effective = true;
+    return 0;
+}
+
 // shift: null for the plain product of A (lam_hip_gemv_many*, and a batch without shifts: the SHIFT = false instantiation, the only
 // one there was), else the K shifts of the batch (MultiState::shift): Y_j = (A + s_j I) P_j
+// Under option "symmetric_many" (K <= 4) the launch site runs the two passes of the symmetric batched product instead
+// (multi_sym_launch): one more launch, and ceil(n / 32) partials per column instead of multi_gemv_grid(c) -- multi_product_blocks.
 template <typename TA, typename TV, int K>
 int multi_launch_gemv(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const MultiScalars *sc, const double *shift = nullptr)
 {
     ShardBase &s = c->sh[0];
+    if constexpr (K <= kSymvManyMaxK)
+        if (multi_sym_wanted(c, K)) return multi_sym_launch<TA, TV, K>(c, P, Y, partial, sc, shift);
+    c->symv_many_effective = false;
     MultiGemvArgs<TA, TV> a;
     a.A = (const TA *)s.A; a.p = P; a.y = Y; a.partial = partial; a.sc = sc;
     a.nrows = c->n; a.ncols = c->ncols_vec(); a.lda = c->lda;
@@ -475,6 +589,11 @@ void multi_report(lam_hip_ctx *c, const MultiScalars &h, F &&rel_of, double t0, 
         st->t_comm_init = c->t_comm_init;
         // the product launch alone, with or without the preconditioner: the diagonal is read by the two vector launches
         st->gemv_bytes = (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n;
+        // the symmetric batched product: the upper triangle once, the vectors as before, the K-wide partials written and read
+        if (c->symv_many_effective)
+            st->gemv_bytes = (double)c->esz_a() * ((double)c->n * ((double)c->n + 1.0) / 2.0) + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n +
+                             2.0 * (double)c->esz_v() * (double)m.K *
+                                 ((double)m.sym_rowpart_elems + (double)m.sym_ntasks * (double)kBlock * (16.0 / (double)c->esz_a()));
     }
 }
 
@@ -584,7 +703,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
             return fail(c, LAM_HIP_EINVAL, "%s: the Jacobi preconditioner needs A[i][i] and 1/A[i][i] finite and > 0: row %llu holds %g "
                         "(%llu such rows)", fn, (unsigned long long)g.bad_row, g.bad_value, (unsigned long long)g.bad_count);
     }
-    const int vb = vec_grid(c->n), gb = multi_gemv_grid(c);
+    const int vb = vec_grid(c->n), gb = multi_product_blocks(c, m.K);
     BatchTiming timing;
     LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc, auto form) -> int {
         using I = decltype(impl);
@@ -666,7 +785,7 @@ int minres_solve(lam_hip_ctx *c, const char *fn, const double *sigma, int max_it
     m.solved = false;
     m.ms.valid = false;
     MinresState &mr = m.mr;
-    const int vb = vec_grid(c->n), gb = multi_gemv_grid(c);
+    const int vb = vec_grid(c->n), gb = multi_product_blocks(c, m.K);
     BatchTiming timing;
     LAMCHK(multi_dispatch(c, m.K, [&](auto impl, auto kc) -> int {
         using I = decltype(impl);

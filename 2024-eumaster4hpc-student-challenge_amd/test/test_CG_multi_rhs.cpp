@@ -1,6 +1,6 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
-//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m] [-Y 0|1|2]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
@@ -15,6 +15,9 @@
 // -m: batched MINRES (lam_hip_solve_many_minres) in place of CG, from x = 0 and without a preconditioner; with it -S takes finite
 // shifts of EITHER sign (without it a negative shift is refused as ever).  Same CSV columns; -T measures under the shifts.  -m with
 // -J, -w or -M is refused.
+// -Y 0|1|2: option "symmetric_many" of the solver's context (the batched product reads every pair of the matrix once; tridiag(1,2,1)
+// is symmetric).  After the solve one line on STDERR says which product the last batched launch ran ("symmetric_many_effective"), so
+// the CSV stays as it is; with more than 4 columns the option is not effective and the run proceeds on the general product.
 // Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
@@ -32,9 +35,28 @@
 
 #include "LAM.hpp"
 
+// -Y: set the option in front of the solve (sym < 0: no -Y, nothing is touched) ...
+static bool set_symmetric_many(lam_hip_ctx *ctx, int sym)
+{
+    if (sym < 0) return true;
+    if (ctx != nullptr && lam_hip_set_option(ctx, "symmetric_many", sym) == 0) return true;
+    fprintf(stderr, "Failed to set option symmetric_many = %d\n", sym);
+    return false;
+}
+// ... and say behind it which product ran
+static void report_symmetric_many(lam_hip_ctx *ctx, int sym)
+{
+    if (sym < 0 || ctx == nullptr) return;
+    int64_t eff = 0, k = 0;
+    lam_hip_get_option(ctx, "symmetric_many_effective", &eff);
+    lam_hip_get_option(ctx, "multi_rhs_k", &k);
+    fprintf(stderr, "symmetric_many = %d, symmetric_many_effective = %lld: K = %lld ran on the %s batched product%s\n", sym, (long long)eff,
+            (long long)k, eff ? "symmetric" : "general", !eff && sym != 0 && k > 4 ? " (the option is not effective for more than 4 columns)" : "");
+}
+
 template <typename T>
 static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jacobi, int warm, bool true_res, const std::vector<double> &shifts,
-               bool minres)
+               bool minres, int sym)
 {
     using clk = std::chrono::high_resolution_clock;
     LAM::ConjugateGradient_HIP<T> cg(0);
@@ -45,6 +67,7 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
         return 1;
     }
     const double t_load = std::chrono::duration<double>(clk::now() - t0).count();
+    if (!set_symmetric_many(cg.context(), sym)) return 3;
     std::vector<T> B((size_t)nrhs * rows);
     for (int j = 0; j < nrhs; j++)
         for (size_t i = 0; i < rows; i++) B[(size_t)j * rows + i] = shifts.empty() ? (T)(double)(1u << j) : (T)1;
@@ -75,6 +98,7 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
         if (cg.batch_failed()) return 3;               // the solve itself failed (reported on stderr)
     }
     const double t_cg = std::chrono::duration<double>(clk::now() - t1).count();
+    report_symmetric_many(cg.context(), sym);
     std::vector<double> tres(nrhs);
     if (true_res && !cg.true_residual_many(nrhs, tres.data())) return 3;
     const lam_hip_stats &st = cg.stats();
@@ -90,7 +114,7 @@ static int run(size_t rows, int nrhs, int max_iters, double rel_error, bool jaco
 
 // -M: every shift of -S against the one right-hand side b = 1 by multi-shift CG
 template <typename T>
-static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_res, const std::vector<double> &shifts)
+static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_res, const std::vector<double> &shifts, int sym)
 {
     using clk = std::chrono::high_resolution_clock;
     const int ns = (int)shifts.size();
@@ -102,6 +126,7 @@ static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_re
         return 1;
     }
     const double t_load = std::chrono::duration<double>(clk::now() - t0).count();
+    if (!set_symmetric_many(cg.context(), sym)) return 3;
     const std::vector<T> b(rows, (T)1);
     std::vector<int32_t> iters(ns), conv(ns);
     std::vector<double> rel(ns), tres(ns);
@@ -109,6 +134,7 @@ static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_re
     cg.solve_mshift(ns, shifts.data(), b.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data());
     if (cg.batch_failed()) return 3;
     const double t_cg = std::chrono::duration<double>(clk::now() - t1).count();
+    report_symmetric_many(cg.context(), sym);
     if (true_res && !cg.true_residual_mshift(ns, tres.data())) return 3;
     const lam_hip_stats &st = cg.stats();
     for (int j = 0; j < ns; j++) {
@@ -147,9 +173,11 @@ int main(int argc, char **argv)
     const char *precision = "f64";
     bool jacobi = false, true_res = false, mshift = false, minres = false, negative = false;
     int warm = -1;                  // -1: no -w
+    int sym = -1;                   // -1: no -Y
+    bool bad_sym = false;
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:Mmh")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:h")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
@@ -162,14 +190,20 @@ int main(int argc, char **argv)
         case 'S': bad_shifts = !parse_shifts(optarg, &shifts, &negative); break;
         case 'M': mshift = true; break;
         case 'm': minres = true; break;
+        case 'Y': bad_sym = strlen(optarg) != 1 || optarg[0] < '0' || optarg[0] > '2'; sym = optarg[0] - '0'; break;
         default:
             fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
                     "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)] "
                     "[-M (with -S, up to %d shifts: multi-shift CG on one right-hand side; not with -J, -w)] "
-                    "[-m (MINRES in place of CG: -S then takes finite shifts of either sign; not with -J, -w, -M)]\n", argv[0],
+                    "[-m (MINRES in place of CG: -S then takes finite shifts of either sign; not with -J, -w, -M)] "
+                    "[-Y 0|1|2 (option symmetric_many: the batched product of up to 4 columns reads every pair of the matrix once)]\n", argv[0],
                     LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS);
             return opt == 'h' ? 0 : 1;
         }
+    }
+    if (bad_sym) {
+        fprintf(stderr, "Usage: -Y takes 0 (the general batched product), 1 (the symmetric one where it pays) or 2 (always, up to 4 columns)\n");
+        return 1;
     }
     if (minres && (jacobi || warm >= 0 || bad_warm || mshift)) {
         fprintf(stderr, "Usage: -m takes neither -J, -w nor -M: MINRES has no preconditioner, starts from x = 0 and is not multi-shift\n");
@@ -195,8 +229,8 @@ int main(int argc, char **argv)
             fprintf(stderr, "Usage: %s -s N -i max_iters [-e rel_error] [-t f64|f32] [-T] -S s0,s1,... -M\n", argv[0]);
             return 1;
         }
-        if (!strcmp(precision, "f64")) return run_mshift<double>(rows, max_iters, rel_error, true_res, shifts);
-        if (!strcmp(precision, "f32")) return run_mshift<float>(rows, max_iters, rel_error, true_res, shifts);
+        if (!strcmp(precision, "f64")) return run_mshift<double>(rows, max_iters, rel_error, true_res, shifts, sym);
+        if (!strcmp(precision, "f32")) return run_mshift<float>(rows, max_iters, rel_error, true_res, shifts, sym);
         fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
         return 1;
     }
@@ -206,8 +240,8 @@ int main(int argc, char **argv)
                 argv[0], LAM_HIP_MAX_RHS);
         return 1;
     }
-    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts, minres);
-    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts, minres);
+    if (!strcmp(precision, "f64")) return run<double>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts, minres, sym);
+    if (!strcmp(precision, "f32")) return run<float>(rows, nrhs, max_iters, rel_error, jacobi, warm, true_res, shifts, minres, sym);
     fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
     return 1;
 }

@@ -54,7 +54,9 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_SHIFTS, lam_hip_solve_mshift, lam_hip_get_solution_mshift and
  *      lam_hip_true_residual_mshift.
  *      Added under version 4 likewise (purely additive): lam_hip_solve_many_minres.  One new refusal becomes reachable with it: a
- *      CG batch call while a negative shift (which only lam_hip_solve_many_minres accepts) is in force. */
+ *      CG batch call while a negative shift (which only lam_hip_solve_many_minres accepts) is in force.
+ *      Added under version 4 likewise (purely additive): option "symmetric_many" and the get-only option "symmetric_many_effective".
+ *      With "symmetric_many" at its default 0 every result is what it was. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -232,7 +234,15 @@ int lam_hip_true_residual(lam_hip_ctx *ctx, double *rel_res);
  *   - supported: single-process contexts with ONE shard, LAM_HIP_F64 and LAM_HIP_F32.  Several shards, rank mode,
  *     LAM_HIP_BF16 and nrhs outside 1..LAM_HIP_MAX_RHS are refused with LAM_HIP_EINVAL and a message that names what is
  *     unsupported; calls before the matrix / the right-hand sides are set give LAM_HIP_ESTATE;
- *   - option "symmetric" (and LAM_HIP_SYMMETRIC) does NOT apply: these entry points always run the general product;
+ *   - option "symmetric" (and LAM_HIP_SYMMETRIC) does not reach these entry points; their own switch is option "symmetric_many"
+ *     (lam_hip_set_option), default 0 = the general batched product.  Under it the product of K <= 4 columns -- the loop product of
+ *     every batched solve, the guess's A x0, MINRES, the multi-shift seed, lam_hip_true_residual_many, lam_hip_gemv_many and
+ *     lam_hip_gemv_many_only -- reads every pair {A[i][j], A[j][i]} once, in two launches instead of one ("hip_calls_launch" counts
+ *     it); K = 8, and with it lam_hip_true_residual_mshift, always runs the general product.  Column j of the symmetric batched
+ *     product is bit for bit lam_hip_gemv's under "symmetric" = 2 for that vector, whatever K and whatever the other columns hold.
+ *     stats.gemv_bytes then reports esz (N (N + 1) / 2 + 2 K N) + 2 esz K (row partials + column partials), the partials being
+ *     those of the single symmetric product's plan (one per row of every task + 256 * (16 / esz) per task), written once and read
+ *     once; t_gemv brackets both launches;
  *   - kernels exist for K = 1, 2, 4 and 8 columns; nrhs runs on the smallest K >= nrhs with zero padding columns that are never
  *     updated (get-only option "multi_rhs_k": the K the last batched call ran, 0 before the first);
  *   - the batch state (vectors, scalars, progress word) is the context's own, allocated at the first batched call and independent of
@@ -515,6 +525,14 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *                   (2(P-1)+1 runtime calls), 0 = every stream waits for every other one (P(P-1)).  Same bits.
  *   "overlap"       rank mode, exchange 0: 1 (default) = all-gather of p on a second stream under the own-slice GEMV panel.
  *                   Exchange 2: 1 = own-slice panel in front of the wait for the peers' slices, 0 = wait first.
+ *   "symmetric_many" the batched product (lam_hip_*_many*, lam_hip_solve_mshift's seed) of K <= 4 columns reads every pair once, as
+ *                   "symmetric" does for one vector: 0 (default) = the general batched product, bit for bit as before; 2 = always;
+ *                   1 = only where it measured faster (a matrix of 192 MiB or more, as "symmetric" has it, and an admitted
+ *                   (dtype, K): fp64 and fp32 at K = 1, 2, 4 all are).  Any other value: LAM_HIP_EINVAL, the value in
+ *                   force stays.  Setting it is the caller's statement that A = A^T (lam_hip_check_symmetry measures it); no
+ *                   environment variable, no automatic check.  One shard, fp64 / fp32, as the batch itself.
+ *                   "symmetric_many_effective" (get): 1 if the last batched product launch ran the symmetric kernels, else 0
+ *                   (before the first batched product, at K = 8, under value 1 below the threshold).
  *   "symmetric"     the product reads every pair {A[i][j], A[j][i]} ONCE (A must equal its transpose): half the HBM traffic.
  *                   One shard: the upper triangle; several (exchange 1): cyclic half windows per row, each shard contributes
  *                   a full-length vector to the exchange.  1 = where it pays (from 192 MiB of matrix on), 2 = always, 0
