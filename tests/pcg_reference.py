@@ -16,9 +16,10 @@ def jacobi_dinv(A, dtype=np.float64):
     return (1.0 / d.astype(np.float64)).astype(dtype)
 
 
-def pcg(A, b, max_iters, rel_error, dinv=None, dtype=np.float64):
+def pcg(A, b, max_iters, rel_error, dinv=None, dtype=np.float64, track=None):
     """Returns (x, stats) with stats = num_iters (max_iters + 1 at the cap), converged, rel_err = sqrt(rr/bb).
-    dinv=None: no preconditioner (dinv = 1)."""
+    dinv=None: no preconditioner (dinv = 1).  track: a dict whose keys are iteration numbers k; track[k] becomes (x, rel_err) as
+    they stand after iteration k -- what the run capped at k returns, bit for bit, as long as the tolerance stops nothing."""
     A = np.ascontiguousarray(A, dtype=dtype)
     b = np.ascontiguousarray(b, dtype=dtype).reshape(-1)
     n = b.size
@@ -37,6 +38,8 @@ def pcg(A, b, max_iters, rel_error, dinv=None, dtype=np.float64):
             x = alpha * p + x
             r = -alpha * Ap + r
             rr = _dot64(r, r)
+            if track is not None and k in track:
+                track[k] = (x.copy(), float(np.sqrt(rr / bb)))
             z = dinv * r
             rz_new = _dot64(r, z)
             if np.sqrt(rr / bb) < rel_error:
@@ -131,9 +134,9 @@ def _sum_order(T, order):
     return lanes.sum(axis=-1, dtype=T.dtype)
 
 
-def pcg_ordered(A, b, max_iters, rel_error, dinv=None, dtype=np.float64, order="rows"):
+def pcg_ordered(A, b, max_iters, rel_error, dinv=None, dtype=np.float64, order="rows", track=None):
     """pcg() statement for statement, with A @ p formed as rounded products summed in the vector dtype in the order `order` (no
-    BLAS: the same bits on every machine) and the fp64 dot products summed in that order too."""
+    BLAS: the same bits on every machine) and the fp64 dot products summed in that order too.  track: as in pcg()."""
     A = np.ascontiguousarray(A, dtype=dtype)
     b = np.ascontiguousarray(b, dtype=dtype).reshape(-1)
     n = b.size
@@ -156,6 +159,8 @@ def pcg_ordered(A, b, max_iters, rel_error, dinv=None, dtype=np.float64, order="
             x = alpha * p + x
             r = -alpha * Ap + r
             rr = dot(r, r)
+            if track is not None and k in track:
+                track[k] = (x.copy(), float(np.sqrt(rr / bb)))
             z = dinv * r
             rz_new = dot(r, z)
             if np.sqrt(rr / bb) < rel_error:

@@ -79,30 +79,47 @@ def test_gemv_generic_path_agrees_with_tiled(lam):
     assert np.array_equal(y_fast, y_plain)      # same kernel, same order: bit-identical
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 1000, 65536, 1 << 20])
-def test_dot_axpby_match_oracle(lam, oracle, n):
+def _with_float_contexts(sizes):
+    """(n, dtype): the fp64 context under the id it always had (n alone), then the contexts whose vectors are float."""
+    return [pytest.param(n, d, id=str(n) if d == "F64" else f"{n}-{d}") for d in ("F64", "F32", "BF16") for n in sizes]
+
+
+@pytest.mark.parametrize("n,dtype_name", _with_float_contexts([1, 63, 64, 1000, 65536, 1 << 20]))
+def test_dot_axpby_match_oracle(lam, oracle, n, dtype_name):
+    """F32 and BF16 contexts keep float vectors: the dot product is formed in fp64 from the stored values (held to the fp64 oracle's
+    on them with the fp64 bound), axpby in fp32 (<= 1 ulp of fp32 against the float oracle)."""
     rng = np.random.default_rng(n)
     x, y = rng.uniform(-1, 1, n), rng.uniform(-1, 1, n)
-    with lam.Solver(lam.F64) as s:
+    with lam.Solver(getattr(lam, dtype_name)) as s:
+        x, y = x.astype(s.vec_dtype), y.astype(s.vec_dtype)
         d = s.dot(x, y)
         z = s.axpby(1.5, x, -0.25, y)
-    assert abs(d - oracle.dot(x, y)) <= 1e-13 * float(np.abs(x) @ np.abs(y))
     z_ref = oracle.axpby(1.5, x, -0.25, y)
-    np.testing.assert_allclose(z, z_ref, rtol=4e-16, atol=0)   # FMA contraction: <= 1 ulp
+    if dtype_name == "F64":
+        assert abs(d - oracle.dot(x, y)) <= 1e-13 * float(np.abs(x) @ np.abs(y))
+        np.testing.assert_allclose(z, z_ref, rtol=4e-16, atol=0)   # FMA contraction: <= 1 ulp
+    else:
+        x64, y64 = x.astype(np.float64), y.astype(np.float64)
+        assert abs(d - oracle.dot(x64, y64)) <= 1e-13 * float(np.abs(x64) @ np.abs(y64))
+        assert z.dtype == z_ref.dtype == np.float32
+        np.testing.assert_allclose(z, z_ref, rtol=2.0 ** -23, atol=0)   # <= 1 ulp of fp32
 
 
-@pytest.mark.parametrize("n", [1, 255, 65536, 1 << 20])
-def test_dot_axpby_are_exact_on_integer_data(lam, n):
+@pytest.mark.parametrize("n,dtype_name", _with_float_contexts([1, 255, 65536, 1 << 20]))
+def test_dot_axpby_are_exact_on_integer_data(lam, n, dtype_name):
     """dot (ConjugateGradient_CPU_MPI_OMP.hpp:446-467) and axpby (:469-480) on small integers: every product and partial sum is an
     exactly representable integer, so the two-stage GPU reduction must return the closed forms BIT FOR BIT whatever its order:
-    sum i = n (n + 1) / 2, sum i^2 = n (n + 1) (2 n + 1) / 6 (n <= 65536: below 2^53), 2 x - 3 y elementwise."""
-    x = np.arange(1, n + 1, dtype=np.float64)
-    with lam.Solver(lam.F64) as s:
-        assert s.dot(x, np.ones(n)) == n * (n + 1) // 2
+    sum i = n (n + 1) / 2, sum i^2 = n (n + 1) (2 n + 1) / 6 (n <= 65536: below 2^53), 2 x - 3 y elementwise.  In F32 and BF16
+    contexts the vectors are float: the entries (<= 2^20) and 2 x - 3 y (below 2^24 in magnitude) are fp32 numbers, and the dot
+    product is formed in fp64 from them, so the same closed forms hold."""
+    with lam.Solver(getattr(lam, dtype_name)) as s:
+        x = np.arange(1, n + 1, dtype=s.vec_dtype)
+        assert 5 * n < 2 ** 24 and x[-1] == n
+        assert s.dot(x, np.ones(n, dtype=s.vec_dtype)) == n * (n + 1) // 2
         if n <= 65536:
             assert s.dot(x, x) == n * (n + 1) * (2 * n + 1) // 6
         z = s.axpby(2.0, x, -3.0, x[::-1].copy())
-    assert np.array_equal(z, 2.0 * x - 3.0 * x[::-1])
+    assert z.dtype == x.dtype and np.array_equal(z, 2.0 * x.astype(np.float64) - 3.0 * x[::-1].astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -190,7 +207,11 @@ def test_cg_matches_oracle_iteration_by_iteration(lam, oracle):
 
     Tolerances come from the reference algorithm's own sensitivity to summation order on this system
     (oracle at 1 thread vs the oracle with 4/8 threads or 3 emulated ranks): <= 1.6e-14 in the residual
-    and <= 2.4e-12 in x up to k=40, then chaotic (4e-3 / 4e-6 at k=60: orthogonality is lost)."""
+    and <= 2.4e-12 in x up to k=40, then chaotic (4e-3 / 4e-6 at k=60: orthogonality is lost).
+
+    This is fp64 on one shard with the default product at n = 384; tests/test_gpu_single_recurrence.py follows the other storage
+    types (fp32, bf16), 2 ... 33 shards on both exchanges, the symmetric product and the two-kernel vector step the same way, on
+    this system and on an n = 1547 one."""
     A, b = iteration_tracking_system()
     with lam.Solver(lam.F64) as s:
         s.set_matrix(A)
