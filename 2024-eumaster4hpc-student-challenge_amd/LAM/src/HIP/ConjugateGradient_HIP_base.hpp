@@ -416,6 +416,53 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         return true;
     }
 
+    // Lanczos eigensolver (lam_hip_eigs): nev extreme eigenpairs of the matrix held, `which` = LAM_HIP_EIG_SMALLEST / _LARGEST /
+    // _BOTH, at most max_steps steps from the start vector v0 (null: lam_hip_generate_random_rhs(seed)'s).  theta / bound / converged:
+    // nev entries each, any may be null; *nfound (may be null) the pairs found.  Returns true iff all nev pairs were found and
+    // converged; batch_failed() as for solve_many.  Members of their own for solve_many's reason.
+    bool eigs(int which, int nev, int max_steps, double tol, int check_every, const FloatingType *v0, uint64_t seed, int32_t *nfound,
+              double *theta, double *bound = nullptr, int32_t *converged = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        lam_hip_stats st;
+        int32_t nf = 0;
+        if (lam_hip_eigs(_ctx, which, nev, max_steps, tol, check_every, v0, seed, &st, &nf, theta, bound, converged) != 0) return report("eigs");
+        _stats = st;
+        _eig_found = nf;
+        if (nfound != nullptr) *nfound = nf;
+        _batch_failed = false;
+        return st.converged != 0;
+    }
+    int eig_found() const { return _eig_found; }               // pairs the last eigs found
+    // the first nev Ritz vectors of the last eigs, pair i at Y + i * cols
+    bool get_eigenvectors(int nev, FloatingType *Y)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_get_eigenvectors(_ctx, nev, Y) != 0) return report("get_eigenvectors");
+        _batch_failed = false;
+        return true;
+    }
+    // ||A y_i - theta_i y_i|| / ||y_i|| of the first nev pairs of the last eigs, formed on the device
+    bool eig_residuals(int nev, double *res)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_eig_residuals(_ctx, nev, res) != 0) return report("eig_residuals");
+        _batch_failed = false;
+        return true;
+    }
+    // *steps, alpha[steps], beta[steps] of the last eigs (room for LAM_HIP_MAX_LANCZOS each)
+    bool get_lanczos(int32_t *steps, double *alpha, double *beta)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_get_lanczos(_ctx, steps, alpha, beta) != 0) return report("get_lanczos");
+        _batch_failed = false;
+        return true;
+    }
+
     // rows held by this process (all of them in the single-process classes), like the reference getters
     size_t get_num_rows() const
     {
@@ -498,6 +545,7 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
     bool _gemv_plus_comm = [] { const char *v = getenv("LAM_CSV_GEMV_PLUS_COMM"); return v && *v && *v != '0'; }();
     lam_hip_stats _stats{};
     bool _batch_failed = false;
+    int _eig_found = 0;
     std::vector<double> _shifts;      // set_shifts_many: empty = none
     bool _shifts_pending = false;     // changed since they were last handed to the library
 };

@@ -18,6 +18,8 @@ F64, F32, BF16 = 0, 1, 2
 ABI_VERSION = 4     # include/lam_hip.h LAM_HIP_ABI_VERSION
 MAX_RHS = 8         # include/lam_hip.h LAM_HIP_MAX_RHS
 MAX_SHIFTS = 64     # include/lam_hip.h LAM_HIP_MAX_SHIFTS
+MAX_LANCZOS = 256   # include/lam_hip.h LAM_HIP_MAX_LANCZOS
+EIG_WHICH = {"smallest": 0, "largest": 1, "both": 2}   # include/lam_hip.h LAM_HIP_EIG_*
 PC_NONE, PC_JACOBI = 0, 1   # include/lam_hip.h LAM_HIP_PC_*: preconditioner of Solver.solve_many / solve_all
 _VEC_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
 _HOST_MAT_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
@@ -143,6 +145,14 @@ def lib():
                                       C.POINTER(C.c_int32), C.POINTER(C.c_double)], i32),
             "lam_hip_get_solution_mshift": ([vp, i32, vp], i32),
             "lam_hip_true_residual_mshift": ([vp, i32, C.POINTER(C.c_double)], i32),
+            "lam_hip_eigs": ([vp, i32, i32, i32, C.c_double, i32, vp, u64, C.POINTER(Stats), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)], i32),
+            "lam_hip_get_lanczos": ([vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "lam_hip_get_eigenvectors": ([vp, i32, vp], i32),
+            "lam_hip_eig_residuals": ([vp, i32, C.POINTER(C.c_double)], i32),
+            "lam_hip_project_out": ([vp, u64, i32, vp, vp, C.POINTER(C.c_double)], i32),
+            "lam_hip_tridiag_eigen": ([i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
             "lam_hip_check_symmetry": ([vp, C.POINTER(C.c_double)], i32),
             "lam_hip_debug_symv_plan": ([u64, i32, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)], i32),
             "lam_hip_dot": ([vp, vp, vp, u64, C.POINTER(C.c_double)], i32),
@@ -198,6 +208,27 @@ def symv_plan_check(n, shards, dtype=0):
     if rc != 0:
         raise LamHipError(rc, "lam_hip_debug_symv_plan")
     return bp.value, bi.value, nt.value
+
+
+def tridiag_eigen(alpha, beta, vectors=False):
+    """Eigenvalues (ascending) of the symmetric tridiagonal matrix with diagonal alpha[k] and off-diagonal beta[:k-1], and the
+    bottom components of its eigenvectors (lam_hip_tridiag_eigen: host only, no GPU, the routine Solver.eigs calls).  Returns
+    (theta, last_row), or with vectors=True (theta, last_row, S) with S[:, i] eigenvector i."""
+    a = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    k = a.size
+    b = np.zeros(max(k, 1), np.float64)
+    bb = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+    if bb.size < k - 1:
+        raise ValueError("tridiag_eigen: beta needs at least len(alpha) - 1 entries")
+    b[:max(k - 1, 0)] = bb[:max(k - 1, 0)]
+    theta, row = np.zeros(max(k, 1), np.float64), np.zeros(max(k, 1), np.float64)
+    S = np.zeros((max(k, 1), max(k, 1)), np.float64) if vectors else None
+    dp = C.POINTER(C.c_double)
+    rc = lib().lam_hip_tridiag_eigen(k, a.ctypes.data_as(dp), b.ctypes.data_as(dp), theta.ctypes.data_as(dp), row.ctypes.data_as(dp),
+                                     S.ctypes.data_as(dp) if vectors else None)
+    if rc != 0:
+        raise LamHipError(rc, "lam_hip_tridiag_eigen: k outside 1..MAX_LANCZOS or a non-finite entry")
+    return (theta[:k], row[:k], S.T.copy()) if vectors else (theta[:k], row[:k])
 
 
 def partition(n, num_shards, shard):
@@ -586,7 +617,68 @@ class Solver:
         self._chk(self._L.lam_hip_gemv_many_only(self._h, nrhs, reps, C.byref(v)))
         return v.value
 
+    # -- Lanczos eigensolver (one shard, F64 / F32) ---------------------------------------------
+    def eigs(self, nev, which="smallest", max_steps=None, tol=None, check_every=8, v0=None, seed=0):
+        """Extreme eigenpairs of the matrix by Lanczos with full reorthogonalisation (lam_hip_eigs).  which: "smallest", "largest",
+        "both" (or the LAM_HIP_EIG_* value); max_steps defaults to min(N, MAX_LANCZOS), tol to 1e-10 (F64) / 1e-5 (F32); v0: a start
+        vector of N elements, or None for generate_random_rhs(seed)'s.  Returns a dict: theta, bound, converged (nev entries, NaN /
+        NaN / False past the pairs found), steps, nfound, stats."""
+        w = EIG_WHICH[which] if isinstance(which, str) else int(which)
+        if max_steps is None:
+            max_steps = min(self.n, MAX_LANCZOS)
+        if tol is None:
+            tol = 1e-10 if self.dtype == F64 else 1e-5
+        v0p = None
+        if v0 is not None:
+            v0 = np.ascontiguousarray(v0, dtype=self.vec_dtype).reshape(-1)
+            assert v0.size == self.n, "the start vector has N elements"
+            v0p = v0.ctypes.data_as(C.c_void_p)
+        k = max(int(nev), 1)
+        th, bd, cv = np.zeros(k, np.float64), np.zeros(k, np.float64), np.zeros(k, np.int32)
+        nf, st = C.c_int32(0), Stats()
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lam_hip_eigs(self._h, w, nev, max_steps, tol, check_every, v0p, seed, C.byref(st), C.byref(nf),
+                                       th.ctypes.data_as(dp), bd.ctypes.data_as(dp), cv.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.stats = st.asdict()
+        self.nfound = nf.value
+        return {"theta": th, "bound": bd, "converged": cv.astype(bool), "steps": st.num_iters, "nfound": nf.value, "stats": self.stats}
+
+    def eigenvectors(self):
+        """(nfound, N): row i is the Ritz vector of pair i of the last eigs, in theta's order."""
+        k = getattr(self, "nfound", 0)
+        Y = np.empty((max(k, 1), self.n), dtype=self.vec_dtype)
+        self._chk(self._L.lam_hip_get_eigenvectors(self._h, k, Y.ctypes.data_as(C.c_void_p)))
+        return Y[:k]
+
+    def eig_residuals(self):
+        """||A y_i - theta_i y_i|| / ||y_i|| of every pair found by the last eigs, formed on the device (lam_hip_eig_residuals)."""
+        k = getattr(self, "nfound", 0)
+        r = np.zeros(max(k, 1), np.float64)
+        self._chk(self._L.lam_hip_eig_residuals(self._h, k, r.ctypes.data_as(C.POINTER(C.c_double))))
+        return r[:k].copy()
+
+    def lanczos_coefficients(self):
+        """(alpha, beta) of the last eigs, `steps` entries each; beta[k] is the norm that made v_{k+1}."""
+        a, b = np.zeros(MAX_LANCZOS, np.float64), np.zeros(MAX_LANCZOS, np.float64)
+        ns = C.c_int32(0)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lam_hip_get_lanczos(self._h, C.byref(ns), a.ctypes.data_as(dp), b.ctypes.data_as(dp)))
+        return a[:ns.value].copy(), b[:ns.value].copy()
+
     # -- single operators -----------------------------------------------------------------------
+    def project_out(self, V, u):
+        """One pass of the eigensolver's reorthogonalisation (lam_hip_project_out): V (m, n), u (n).  Returns (coeff, u_new) with
+        coeff[j] = V[j].u and u_new = u - sum_j coeff[j] V[j] in the vector dtype."""
+        V = np.ascontiguousarray(V, dtype=self.vec_dtype)
+        if V.ndim == 1:
+            V = V.reshape(1, -1)
+        u = np.ascontiguousarray(u, dtype=self.vec_dtype).reshape(-1).copy()
+        assert V.ndim == 2 and V.shape[1] == u.size, "V is (m, n), u has n elements"
+        coeff = np.zeros(max(V.shape[0], 1), np.float64)
+        self._chk(self._L.lam_hip_project_out(self._h, u.size, V.shape[0], V.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p),
+                                              coeff.ctypes.data_as(C.POINTER(C.c_double))))
+        return coeff[:V.shape[0]], u
+
     def gemv(self, x):
         x = np.ascontiguousarray(x, dtype=self.vec_dtype).reshape(-1)
         assert x.size == self.n

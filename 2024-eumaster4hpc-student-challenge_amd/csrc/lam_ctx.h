@@ -105,7 +105,26 @@ struct MinresState {
     MinresScalars *sc = nullptr;             // device; the last of the three to be allocated: set means all are
 };
 
+// lam_hip_eigs (lam_eigs.h): the Lanczos basis, u, the Ritz vectors and the scalars, next to the batch's vectors and independent of
+// its right-hand sides and shifts.  Allocated by the first call for the batch's n, grow-only in max_steps (cap), released with the
+// batch (multi_release).  What the host keeps of the last run is what the getters serve.
+struct LanczosState {
+    void *V = nullptr;           // (cap + 1) rows of `pitch` elements, zero behind element n of every row
+    void *U = nullptr;           // n elements (+ padding)
+    void *Y = nullptr;           // cap Ritz vectors of n elements, pair i contiguous at i * n
+    double *part = nullptr;      // [cap + 1][kVecBlocksMax] partials of the projection's dots
+    double *part_uu = nullptr;   // [kVecBlocksMax] partials of u.u (and of v0.v0)
+    double *S = nullptr;         // device, cap * cap: the wanted columns of the tridiagonal's eigenvector matrix
+    LanczosScalars *sc = nullptr;// device; the last to be allocated: set means all are
+    int cap = 0;
+    uint64_t pitch = 0;          // elements between basis rows
+    bool valid = false;          // an eigen-solution is readable
+    int steps = 0, nfound = 0;   // of the last run
+    std::vector<double> alpha, beta, theta;   // alpha[steps], beta[steps]; theta[nfound] in the order `which` asked for
+};
+
 struct MultiState {
+    LanczosState lz;
     uint64_t n = 0;             // the problem size the buffers were allocated for (0: none)
     void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out
@@ -359,7 +378,7 @@ void matrix_changed(lam_hip_ctx *c)
     c->cg_ready = false;
     c->matrix_gen++;
     c->sym_refused = false;
-    c->multi.solved = c->multi.ms.valid = false;
+    c->multi.solved = c->multi.ms.valid = c->multi.lz.valid = false;
 }
 
 // ConjugateGradient_CPU_MPI_OMP.hpp:176-184: n/P rows each, the remainder on the LAST rank (lam_host_plan.h)

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "lam_host_plan.h"
+#include "lam_host_tridiag.h"
 
 namespace lam {
 
@@ -3612,6 +3613,314 @@ mshift_residual_kernel(const TV *__restrict__ B, const TV *__restrict__ Y, uint6
         if (threadIdx.x == 0) {
             partial_rr[(size_t)j * gridDim.x + blockIdx.x] = t;
             partial_bb[(size_t)j * gridDim.x + blockIdx.x] = tb;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Lanczos (lam_hip_eigs, lam_eigs.h): extreme eigenpairs of A from a Lanczos recurrence with FULL reorthogonalisation, one product
+// per step.  The recurrence is stated in include/lam_hip.h.  Step `step` (counted from 1; k = step - 1) is the K = 1 product launch
+// on basis row v_k (u = A v_k, partials of v_k.u) and six launches of this section:
+//   lanczos_three_term_kernel    alpha_k from the product's partials ; u = fma(-beta_{k-1}, v_{k-1}, fma(-alpha_k, v_k, u))
+//   lanczos_dots_kernel          partial[j][block] of c_j = v_j.u, j = 0..k            \  one pass of classical Gram-Schmidt,
+//   lanczos_apply_kernel         c_j from the partials ; u = fma(-c_j, v_j, u), j up   /  run twice; the second one ends in u.u
+//   lanczos_append_kernel        beta_k = sqrt(u.u), the breakdown rule, v_{k+1} = u * (1 / beta_k), the progress word
+// Basis: row j at V + j * pitch, pitch a 256-byte multiple of n + kMultiPadRows elements, zero behind element n, so a row is the
+// product's input as it stands.  The two projection kernels cut u into one contiguous slab per workgroup (whole 16-byte vectors;
+// the last slab takes the ragged tail element by element): a workgroup reads its slab of u ONCE, holds it in registers
+// (kLanczosHold 16-byte vectors per thread and round; a slab longer than that takes further rounds), and streams the same slab of
+// every basis row past it with 16-byte loads (lanczos_dots_kernel: of the rows its y index is dealt).  All sums are fp64 and of fixed order: lane, wave (wave_sum), the four waves, then
+// the workgroups' partials in block order -- no floating-point atomics, the same bits on every run.
+// Who decides: stopped_at (0: running; else the step whose beta met the breakdown rule) is written by workgroup 0 of that step's
+// append launch alone; every launch of a LATER step returns on it, and the append launch itself recomputes the decision in every
+// workgroup from bits no workgroup of it writes (minres_update_kernel's argument).
+// ---------------------------------------------------------------------------------------------
+constexpr int kLanczosHold = 4;       // 16-byte vectors of u a thread holds per round of a projection kernel
+constexpr int kLanczosSplit = 16;     // gridDim.y of lanczos_dots_kernel: the basis rows are dealt out over this many workgroups per slab
+struct LanczosScalars : MultiScalars {            // the prefix is what the product kernel reads (all_stop)
+    double alpha[kMaxLanczos];        // alpha_k = v_k.(A v_k), the product's fused partials
+    double beta[kMaxLanczos];         // beta_k = ||u|| behind the reorthogonalisation of step k: the norm that made v_{k+1}
+    double tmax[kMaxLanczos];         // max over j <= k of |alpha_j| + beta_{j-1} + beta_j: the breakdown rule's scale
+    double v0norm;                    // ||v0|| of the start vector as given
+    int steps;                        // steps completed
+    int stopped_at;                   // 0, or the step (from 1) at which the Krylov space was found invariant
+};
+
+template <typename TV>
+__device__ __forceinline__ void lanczos_slab(uint64_t n, uint64_t *first, uint64_t *end)
+{
+    constexpr uint64_t VEC = 16 / sizeof(TV);
+    const uint64_t nvec = (n + VEC - 1) / VEC;
+    const uint64_t per = (nvec + gridDim.x - 1) / gridDim.x * VEC;
+    const uint64_t f = (uint64_t)blockIdx.x * per;
+    *first = f < n ? f : n;
+    *end = f + per < n ? f + per : n;
+}
+
+// VEC elements of x from element idx (a multiple of VEC; x 16-byte aligned): one 16-byte load where they all lie in front of `end`,
+// else the ones that do, element by element, and zeros
+template <typename TV>
+__device__ __forceinline__ void lanczos_load(const TV *__restrict__ x, uint64_t idx, uint64_t end, TV (&out)[16 / sizeof(TV)])
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    typedef TV vec_t __attribute__((ext_vector_type(VEC)));
+    if (idx + VEC <= end) {
+        const vec_t v = *reinterpret_cast<const vec_t *>(x + idx);
+#pragma unroll
+        for (int e = 0; e < VEC; e++) out[e] = v[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; e++) out[e] = idx + e < end ? x[idx + e] : (TV)0;
+    }
+}
+template <typename TV>
+__device__ __forceinline__ void lanczos_store(TV *__restrict__ x, uint64_t idx, uint64_t end, const TV (&in)[16 / sizeof(TV)])
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    typedef TV vec_t __attribute__((ext_vector_type(VEC)));
+    if (idx + VEC <= end) {
+        vec_t v;
+#pragma unroll
+        for (int e = 0; e < VEC; e++) v[e] = in[e];
+        *reinterpret_cast<vec_t *>(x + idx) = v;
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; e++)
+            if (idx + e < end) x[idx + e] = in[e];
+    }
+}
+
+__device__ __forceinline__ bool lanczos_over(const LanczosScalars *sc, int step)
+{
+    if (sc == nullptr) return false;
+    const int st = sc->stopped_at;
+    return st != 0 && step > st;
+}
+
+// partials of v0.v0 are dot_partial_kernel's; this one: v_0 = v0 * (1 / ||v0||), the scalars' start, the progress word.  v0 is in u.
+template <typename TV>
+__global__ void __launch_bounds__(kBlock)
+lanczos_start_kernel(const double *__restrict__ red, int nred, LanczosScalars *sc, const TV *__restrict__ u, TV *__restrict__ v0, uint64_t n,
+                     volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    const double nrm = sqrt(block_sum_array(red, nred, s_red));
+    const TV inv = (TV)(1.0 / nrm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int j = 0; j < kMaxRhs; j++) {
+            CgScalars &c = sc->col[j];
+            c.bb = 0.0; c.rr[0] = 0.0; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
+            c.stop = j == 0 ? 0 : 1;
+        }
+        sc->all_stop = 0;
+        sc->pad = 0;
+        sc->v0norm = nrm;
+        sc->steps = 0;
+        sc->stopped_at = 0;
+        post_progress(host_flags, 0, false);
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) v0[i] = u[i] * inv;
+}
+
+template <typename TV>
+__global__ void __launch_bounds__(kBlock)
+lanczos_three_term_kernel(const double *__restrict__ red, int nred, LanczosScalars *sc, int step, const TV *__restrict__ vk,
+                          const TV *__restrict__ vkm1, TV *__restrict__ u, uint64_t n)
+{
+    __shared__ double s_red[kWaves];
+    if (lanczos_over(sc, step)) return;
+    const int k = step - 1;
+    const double alpha = block_sum_array(red, nred, s_red);
+    const TV nalpha = -(TV)alpha;
+    if (k == 0) {
+        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+            u[i] = fma_tv(nalpha, vk[i], u[i]);
+    } else {
+        const TV nbeta = -(TV)sc->beta[k - 1];
+        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+            u[i] = fma_tv(nbeta, vkm1[i], fma_tv(nalpha, vk[i], u[i]));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { sc->alpha[k] = alpha; sc->col[0].alpha = alpha; sc->col[0].pAp = alpha; }
+}
+
+// partial[j * gridDim.x + blockIdx.x] = the workgroup's part of v_j.u; the grid's y dimension deals the rows out: workgroup (x, y) takes
+// the slab x of u and of the rows j = y, y + gridDim.y, ... < m, so the launch has the same shape whatever m is and the stream of V
+// meets gridDim.y times the workgroups a one-dimensional grid of slabs would give it.  sc may be null (lam_hip_project_out).
+template <typename TV>
+__global__ void __launch_bounds__(kBlock)
+lanczos_dots_kernel(const LanczosScalars *sc, int step, const TV *__restrict__ V, uint64_t pitch, int m, const TV *__restrict__ u, uint64_t n,
+                    double *__restrict__ partial)
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    __shared__ double s_acc[kMaxLanczos + 1][kWaves];
+    if (lanczos_over(sc, step)) return;
+    uint64_t first, end;
+    lanczos_slab<TV>(n, &first, &end);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr uint64_t ROUND = (uint64_t)kBlock * VEC * kLanczosHold;
+    bool round0 = true;
+    for (uint64_t base = first; round0 || base < end; base += ROUND) {
+        TV ur[kLanczosHold][VEC];
+#pragma unroll
+        for (int h = 0; h < kLanczosHold; h++) lanczos_load<TV>(u, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, ur[h]);
+#pragma unroll 2
+        for (int j = blockIdx.y; j < m; j += gridDim.y) {
+            const TV *vj = V + (uint64_t)j * pitch;
+            double a = 0.0;
+#pragma unroll
+            for (int h = 0; h < kLanczosHold; h++) {
+                TV vr[VEC];
+                lanczos_load<TV>(vj, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, vr);
+#pragma unroll
+                for (int e = 0; e < VEC; e++) a = __builtin_fma((double)vr[e], (double)ur[h][e], a);
+            }
+            a = wave_sum(a);
+            if (lane == 0) s_acc[j][wave] = round0 ? a : s_acc[j][wave] + a;
+        }
+        round0 = false;
+    }
+    __syncthreads();
+    for (int j = blockIdx.y + threadIdx.x * gridDim.y; j < m; j += kBlock * gridDim.y) {
+        double t = s_acc[j][0];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) t += s_acc[j][w];
+        partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// c_j = the nred partials of column j in block order (the same bits in every workgroup) ; u = fma(-(TV)c_j, v_j, u) for j = 0..m-1
+// in ascending order on the workgroup's slab ; NORM: partial_uu[block] of the new u.u.  coeff (may be null): c_j in fp64, by
+// workgroup 0.
+template <typename TV, bool NORM>
+__global__ void __launch_bounds__(kBlock)
+lanczos_apply_kernel(const LanczosScalars *sc, int step, const double *__restrict__ partial, int nred, const TV *__restrict__ V, uint64_t pitch,
+                     int m, TV *__restrict__ u, uint64_t n, double *__restrict__ coeff, double *__restrict__ partial_uu)
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    __shared__ TV s_nc[kMaxLanczos + 1];
+    __shared__ double s_red[kWaves];
+    if (lanczos_over(sc, step)) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int j = wave; j < m; j += kWaves) {
+        double a = 0.0;
+        for (int b = lane; b < nred; b += 64) a += partial[(size_t)j * nred + b];
+        a = wave_sum(a);
+        if (lane == 0) {
+            s_nc[j] = -(TV)a;
+            if (coeff != nullptr && blockIdx.x == 0) coeff[j] = a;
+        }
+    }
+    __syncthreads();
+    uint64_t first, end;
+    lanczos_slab<TV>(n, &first, &end);
+    constexpr uint64_t ROUND = (uint64_t)kBlock * VEC * kLanczosHold;
+    double acc = 0.0;
+    for (uint64_t base = first; base < end; base += ROUND) {
+        TV ur[kLanczosHold][VEC];
+#pragma unroll
+        for (int h = 0; h < kLanczosHold; h++) lanczos_load<TV>(u, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, ur[h]);
+#pragma unroll 4
+        for (int j = 0; j < m; j++) {
+            const TV *vj = V + (uint64_t)j * pitch;
+            const TV nc = s_nc[j];
+#pragma unroll
+            for (int h = 0; h < kLanczosHold; h++) {
+                TV vr[VEC];
+                lanczos_load<TV>(vj, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, vr);
+#pragma unroll
+                for (int e = 0; e < VEC; e++) ur[h][e] = fma_tv(nc, vr[e], ur[h][e]);
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < kLanczosHold; h++) {
+            lanczos_store<TV>(u, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, ur[h]);
+            if constexpr (NORM) {
+#pragma unroll
+                for (int e = 0; e < VEC; e++) acc = __builtin_fma((double)ur[h][e], (double)ur[h][e], acc);
+            }
+        }
+    }
+    if constexpr (NORM) {
+        const double t = block_sum(acc, s_red);
+        if (threadIdx.x == 0) partial_uu[blockIdx.x] = t;
+    }
+}
+
+// beta_k = sqrt(u.u) ; the Krylov space is invariant if beta_k is 0, not finite or <= scale * max_{j <= k}(|alpha_j| + beta_{j-1} +
+// beta_j), scale = N * (unit roundoff of the vector dtype): the run stops, v_{k+1} is not formed and the progress word says
+// "stopped"; else v_{k+1} = u * (1 / beta_k).
+template <typename TV>
+__global__ void __launch_bounds__(kBlock)
+lanczos_append_kernel(const double *__restrict__ red, int nred, LanczosScalars *sc, int step, double scale, const TV *__restrict__ u,
+                      TV *__restrict__ vnext, uint64_t n, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    if (lanczos_over(sc, step)) return;
+    const int k = step - 1;
+    const double beta = sqrt(block_sum_array(red, nred, s_red));
+    const double alpha = sc->alpha[k];                                   // the three-term launch of this step wrote it
+    const double bprev = k > 0 ? sc->beta[k - 1] : 0.0, tprev = k > 0 ? sc->tmax[k - 1] : 0.0;
+    const double tmax = fmax(tprev, fabs(alpha) + bprev + beta);
+    const bool stop = !(beta > scale * tmax) || !(beta <= std::numeric_limits<double>::max());
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sc->beta[k] = beta;
+        sc->tmax[k] = tmax;
+        sc->col[0].beta = beta;
+        sc->col[0].iters = step;
+        sc->steps = step;
+        if (stop) { sc->stopped_at = step; sc->col[0].stop = 1; sc->all_stop = 1; }
+        post_progress(host_flags, step, stop);
+    }
+    if (stop) return;
+    const TV ib = (TV)(1.0 / beta);
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) vnext[i] = u[i] * ib;
+}
+
+// Ritz vectors: Y[pair][i] = sum_j S[pair][j] V[j][i], fp64 coefficients, fp64 accumulation in ascending j, one rounding to the
+// vector dtype.  S: column `pair` of the tridiagonal's eigenvector matrix contiguous at S + pair * k; Y: pair contiguous at Y + pair * n.
+template <typename TV>
+__global__ void __launch_bounds__(kBlock)
+lanczos_ritz_kernel(const TV *__restrict__ V, uint64_t pitch, int k, const double *__restrict__ S, TV *__restrict__ Y, uint64_t n)
+{
+    __shared__ double s_s[kMaxLanczos];
+    const int pair = blockIdx.y;
+    for (int j = threadIdx.x; j < k; j += kBlock) s_s[j] = S[(size_t)pair * k + j];
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        double acc = 0.0;
+        for (int j = 0; j < k; j++) acc = __builtin_fma(s_s[j], (double)V[(uint64_t)j * pitch + i], acc);
+        Y[(uint64_t)pair * n + i] = (TV)acc;
+    }
+}
+
+// lam_hip_eig_residuals: with AY = A Y from one batched product ([n][K] both), per column the fp64 partials of
+// (A y - theta y).(A y - theta y) and of y.y, both at [j * gridDim.x + block]; multi_residual_scalars_kernel forms the quotients
+struct LanczosTheta { double t[kMaxRhs]; };
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+lanczos_residual_kernel(const TV *__restrict__ Y, const TV *__restrict__ AY, LanczosTheta theta, uint64_t n, double *__restrict__ partial_rr,
+                        double *__restrict__ partial_yy)
+{
+    __shared__ double s_red[kWaves];
+    double acc[K], accy[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = accy[j] = 0.0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const double yi = (double)Y[i * K + j];
+            const double ri = __builtin_fma(-theta.t[j], yi, (double)AY[i * K + j]);
+            acc[j] += ri * ri;
+            accy[j] += yi * yi;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        const double ty = block_sum(accy[j], s_red);
+        if (threadIdx.x == 0) {
+            partial_rr[(size_t)j * gridDim.x + blockIdx.x] = t;
+            partial_yy[(size_t)j * gridDim.x + blockIdx.x] = ty;
         }
     }
 }

@@ -61,6 +61,7 @@ void multi_release(lam_hip_ctx *c)
     free_dev({m.ms.XS, m.ms.PS, m.ms.sc});
     free_dev({m.mr.W, m.mr.WOLD, m.mr.sc});
     free_dev({m.sym_tasks, m.sym_index, m.sym_rowpart, m.sym_colpart});
+    free_dev({m.lz.V, m.lz.U, m.lz.Y, m.lz.part, m.lz.part_uu, m.lz.S, m.lz.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -556,6 +557,19 @@ void multi_harvest(MultiState &m, int slot, BatchTiming *t)
     t->samples++;
 }
 
+// algorithmic bytes of the product launch of instantiation K as it last ran: the product launch alone, with or without the
+// preconditioner (the diagonal is read by the two vector launches); under the symmetric batched product the upper triangle once, the
+// vectors as before, the K-wide partials written and read
+double multi_gemv_bytes(const lam_hip_ctx *c, int K)
+{
+    const MultiState &m = c->multi;
+    if (c->symv_many_effective)
+        return (double)c->esz_a() * ((double)c->n * ((double)c->n + 1.0) / 2.0) + (double)c->esz_v() * 2.0 * (double)K * (double)c->n +
+               2.0 * (double)c->esz_v() * (double)K *
+                   ((double)m.sym_rowpart_elems + (double)m.sym_ntasks * (double)kBlock * (16.0 / (double)c->esz_a()));
+    return (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)K * (double)c->n;
+}
+
 // what a batched solve reports, CG or MINRES: the per-column arrays and the batch's stats from the scalars' prefix as the host read
 // it back; rel_of(j, col) is column j's rel_err (CG: from its r.r ring; MINRES: its own word)
 template <typename F>
@@ -587,13 +601,7 @@ void multi_report(lam_hip_ctx *c, const MultiScalars &h, F &&rel_of, double t0, 
         st->t_iter = ran > 0 ? (t1 - t0) / ran : 0.0;
         st->t_gemv = timing.samples > 0 ? timing.gemv_ms * 1e-3 / timing.samples : 0.0;
         st->t_comm_init = c->t_comm_init;
-        // the product launch alone, with or without the preconditioner: the diagonal is read by the two vector launches
-        st->gemv_bytes = (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n;
-        // the symmetric batched product: the upper triangle once, the vectors as before, the K-wide partials written and read
-        if (c->symv_many_effective)
-            st->gemv_bytes = (double)c->esz_a() * ((double)c->n * ((double)c->n + 1.0) / 2.0) + (double)c->esz_v() * 2.0 * (double)m.K * (double)c->n +
-                             2.0 * (double)c->esz_v() * (double)m.K *
-                                 ((double)m.sym_rowpart_elems + (double)m.sym_ntasks * (double)kBlock * (16.0 / (double)c->esz_a()));
+        st->gemv_bytes = multi_gemv_bytes(c, m.K);
     }
 }
 

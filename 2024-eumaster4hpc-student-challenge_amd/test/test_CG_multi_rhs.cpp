@@ -1,6 +1,7 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m] [-Y 0|1|2]
+//     test_CG_multi_rhs.out -s N -E nev [-W s|l|b] [-i max_steps] [-e tol] [-t f64|f32] [-Y 0|1|2]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
@@ -18,6 +19,12 @@
 // -Y 0|1|2: option "symmetric_many" of the solver's context (the batched product reads every pair of the matrix once; tridiag(1,2,1)
 // is symmetric).  After the solve one line on STDERR says which product the last batched launch ran ("symmetric_many_effective"), so
 // the CSV stays as it is; with more than 4 columns the option is not effective and the run proceeds on the general product.
+// -E nev: the Lanczos eigensolver (lam_hip_eigs) in place of a solve: nev extreme eigenpairs of the matrix, -W s (smallest, the
+// default), l (largest) or b (both ends); -i is max_steps (default min(N, 256)), -e is tol; the start vector is
+// lam_hip_generate_random_rhs(0)'s, convergence is checked every 8 steps.  One CSV line per pair found:
+//     index,theta,bound,residual,converged,steps,t_load,t_comm_init,t_gemv,t_iter,t_cg
+// with residual = ||A y - theta y|| / ||y|| formed on the device (lam_hip_eig_residuals; -T is implied).  -E with -J, -w, -S, -M, -m
+// or -k is a usage error.
 // Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
@@ -146,6 +153,37 @@ static int run_mshift(size_t rows, int max_iters, double rel_error, bool true_re
     return 0;
 }
 
+// -E: nev extreme eigenpairs of the generated matrix by lam_hip_eigs
+template <typename T>
+static int run_eigs(size_t rows, int nev, int which, int max_steps, double tol, int sym)
+{
+    using clk = std::chrono::high_resolution_clock;
+    LAM::ConjugateGradient_HIP<T> cg(0);
+    cg.set_text_output(false);
+    const auto t0 = clk::now();
+    if (!cg.generate_matrix(rows, rows)) {
+        fprintf(stderr, "Failed to generate matrix\n");
+        return 1;
+    }
+    const double t_load = std::chrono::duration<double>(clk::now() - t0).count();
+    if (!set_symmetric_many(cg.context(), sym)) return 3;
+    std::vector<double> theta(nev), bound(nev), res(nev);
+    std::vector<int32_t> conv(nev);
+    int32_t found = 0;
+    const auto t1 = clk::now();
+    cg.eigs(which, nev, max_steps, tol, 8, nullptr, 0, &found, theta.data(), bound.data(), conv.data());
+    if (cg.batch_failed()) return 3;
+    const double t_cg = std::chrono::duration<double>(clk::now() - t1).count();
+    const lam_hip_stats st = cg.stats();
+    report_symmetric_many(cg.context(), sym);
+    if (found > 0 && !cg.eig_residuals(found, res.data())) return 3;
+    std::cout.precision(17);
+    for (int i = 0; i < found; i++)
+        std::cout << i << "," << theta[i] << "," << bound[i] << "," << res[i] << "," << conv[i] << "," << st.num_iters << "," << t_load << ","
+                  << st.t_comm_init << "," << st.t_gemv << "," << st.t_iter << "," << t_cg << std::endl;
+    return 0;
+}
+
 // "s0,s1,...": 1..LAM_HIP_MAX_SHIFTS numbers (main holds a list without -M to LAM_HIP_MAX_RHS), each finite, nothing else; *negative:
 // one of them is < 0, which main accepts under -m only (it decides once every option is parsed)
 static bool parse_shifts(const char *arg, std::vector<double> *out, bool *negative)
@@ -169,6 +207,8 @@ int main(int argc, char **argv)
 {
     size_t rows = 0;
     int nrhs = 1, max_iters = 1000, opt;
+    int nev = 0, which = LAM_HIP_EIG_SMALLEST;      // nev == 0: no -E
+    bool bad_eigs = false, i_given = false, s_given = false;
     double rel_error = 1e-9;
     const char *precision = "f64";
     bool jacobi = false, true_res = false, mshift = false, minres = false, negative = false;
@@ -177,32 +217,56 @@ int main(int argc, char **argv)
     bool bad_sym = false;
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:h")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:E:W:h")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
-        case 'i': max_iters = atoi(optarg); break;
+        case 'i': max_iters = atoi(optarg); i_given = true; break;
         case 'e': rel_error = atof(optarg); break;
         case 't': precision = optarg; break;
         case 'J': jacobi = true; break;
         case 'w': warm = atoi(optarg); bad_warm = warm < 0; break;
         case 'T': true_res = true; break;
-        case 'S': bad_shifts = !parse_shifts(optarg, &shifts, &negative); break;
+        case 'S': bad_shifts = !parse_shifts(optarg, &shifts, &negative); s_given = true; break;
         case 'M': mshift = true; break;
         case 'm': minres = true; break;
+        case 'E': nev = atoi(optarg); bad_eigs = bad_eigs || nev < 1; break;
+        case 'W':
+            if (!strcmp(optarg, "s")) which = LAM_HIP_EIG_SMALLEST;
+            else if (!strcmp(optarg, "l")) which = LAM_HIP_EIG_LARGEST;
+            else if (!strcmp(optarg, "b")) which = LAM_HIP_EIG_BOTH;
+            else bad_eigs = true;
+            break;
         case 'Y': bad_sym = strlen(optarg) != 1 || optarg[0] < '0' || optarg[0] > '2'; sym = optarg[0] - '0'; break;
         default:
             fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
                     "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)] "
                     "[-M (with -S, up to %d shifts: multi-shift CG on one right-hand side; not with -J, -w)] "
                     "[-m (MINRES in place of CG: -S then takes finite shifts of either sign; not with -J, -w, -M)] "
-                    "[-Y 0|1|2 (option symmetric_many: the batched product of up to 4 columns reads every pair of the matrix once)]\n", argv[0],
-                    LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS);
+                    "[-Y 0|1|2 (option symmetric_many: the batched product of up to 4 columns reads every pair of the matrix once)] "
+                    "[-E nev (Lanczos eigensolver lam_hip_eigs in place of a solve: nev extreme eigenpairs; -W s|l|b smallest / largest / both, "
+                    "-i max_steps up to %d, -e tol; not with -J, -w, -S, -M, -m, -k)]\n", argv[0],
+                    LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS, LAM_HIP_MAX_LANCZOS);
             return opt == 'h' ? 0 : 1;
         }
     }
     if (bad_sym) {
         fprintf(stderr, "Usage: -Y takes 0 (the general batched product), 1 (the symmetric one where it pays) or 2 (always, up to 4 columns)\n");
+        return 1;
+    }
+    if (nev != 0 || bad_eigs) {
+        if (bad_eigs || jacobi || warm >= 0 || bad_warm || s_given || mshift || minres || k_given) {
+            fprintf(stderr, "Usage: -E nev (>= 1) [-W s|l|b] takes neither -J, -w, -S, -M, -m nor -k: the eigensolver runs on the matrix alone\n");
+            return 1;
+        }
+        if (!i_given) max_iters = (int)(rows < (size_t)LAM_HIP_MAX_LANCZOS ? rows : (size_t)LAM_HIP_MAX_LANCZOS);
+        if (rows == 0) {
+            fprintf(stderr, "Usage: %s -s N -E nev [-W s|l|b] [-i max_steps] [-e tol] [-t f64|f32] [-Y 0|1|2]\n", argv[0]);
+            return 1;
+        }
+        if (!strcmp(precision, "f64")) return run_eigs<double>(rows, nev, which, max_iters, rel_error, sym);
+        if (!strcmp(precision, "f32")) return run_eigs<float>(rows, nev, which, max_iters, rel_error, sym);
+        fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
         return 1;
     }
     if (minres && (jacobi || warm >= 0 || bad_warm || mshift)) {

@@ -56,7 +56,9 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): lam_hip_solve_many_minres.  One new refusal becomes reachable with it: a
  *      CG batch call while a negative shift (which only lam_hip_solve_many_minres accepts) is in force.
  *      Added under version 4 likewise (purely additive): option "symmetric_many" and the get-only option "symmetric_many_effective".
- *      With "symmetric_many" at its default 0 every result is what it was. */
+ *      With "symmetric_many" at its default 0 every result is what it was.
+ *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_LANCZOS, LAM_HIP_EIG_SMALLEST / _LARGEST / _BOTH, lam_hip_eigs,
+ *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -453,6 +455,75 @@ int lam_hip_get_solution_mshift(lam_hip_ctx *ctx, int nshifts, void *x_host);
  * dtype, fp64 sums; plain IEEE, b = 0 gives 0/0).  Leaves the seed's batch (B, X) and the multi-shift solution readable. */
 int lam_hip_true_residual_mshift(lam_hip_ctx *ctx, int nshifts, double *rel_res);
 
+/* ---- Lanczos eigensolver: extreme eigenpairs of A at one product per step -----------------------
+ * The other question asked of a dense symmetric matrix: its smallest and / or largest eigenvalues and their eigenvectors.  Lanczos
+ * with FULL reorthogonalisation on the context's matrix A -- the plain product, as lam_hip_gemv_many is: the shifts in force are
+ * ignored -- from one start vector, NOT restarted: at most max_steps <= LAM_HIP_MAX_LANCZOS steps.  No reference counterpart.
+ *   - start vector: v0_host, N elements of the vector dtype, or v0_host == NULL: the law of lam_hip_generate_random_rhs(seed)
+ *     (tests/generator_model.py).  It is normalised on the device; a zero or non-finite ||v0|| is LAM_HIP_EINVAL;
+ *   - step k = 0, 1, ..., every scalar fp64:
+ *         u = A v_k                                        the K = 1 product launch of the batch; alpha_k = v_k.u from its fused partials
+ *         u = fma(-beta_{k-1}, v_{k-1}, fma(-alpha_k, v_k, u))
+ *         twice ("twice is enough", classical Gram-Schmidt):  c = V^T u over v_0 .. v_k ;  u = fma(-c_j, v_j, u), j ascending
+ *         beta_k = ||u|| ; unless the breakdown rule stops the run: v_{k+1} = u * (1 / beta_k)
+ *     the coefficients that multiply vectors (alpha, beta, every c_j, the reciprocal) are rounded to the vector dtype once.  T keeps
+ *     the fused alpha_k and the beta_k behind the reorthogonalisation; the Gram-Schmidt corrections are not folded in;
+ *   - every sum goes through per-workgroup partials summed in a fixed order (no floating-point atomics): two calls with the same
+ *     inputs give the same bits;
+ *   - BREAKDOWN: the Krylov space is invariant if at step k beta_k is 0, not finite, or at most
+ *     N u max_{j <= k}(|alpha_j| + beta_{j-1} + beta_j), u the unit roundoff of the vector dtype (2^-53 / 2^-24): the size of the
+ *     rounding error of A v itself, below which u is noise.  v_{k+1} is then not formed, the run stops, the k + 1 Ritz pairs are
+ *     final (reported converged) and nfound = min(nev, k + 1);
+ *   - convergence is tested on the host after every check_every >= 1 steps (else LAM_HIP_EINVAL) and at the end: the stream is
+ *     drained, theta and the bottom row s_{k,i} of T_k's eigenvector matrix come from a QL sweep that carries one row (O(k^2) per
+ *     check), bound_i = beta_k |s_{k,i}|, and pair i is converged when bound_i <= tol * max_j |theta_j| -- relative to the norm,
+ *     because the attainable floor is u ||A|| whatever theta_i is.  The run stops when all wanted pairs are converged, at a breakdown
+ *     or at max_steps; tol <= 0 never stops early;
+ *   - which: LAM_HIP_EIG_SMALLEST (ascending), LAM_HIP_EIG_LARGEST (descending), LAM_HIP_EIG_BOTH (ceil(nev/2) smallest, ascending,
+ *     then floor(nev/2) largest, descending).  theta / bound / converged: nev entries each in that order, entries past *nfound are
+ *     NaN / NaN / 0; any output pointer may be NULL.  stats: num_iters = the steps run, converged = all nev pairs were found and
+ *     converged, rel_err = the worst bound_i / max|theta|, t_gemv / t_iter / t_total / gemv_bytes as for the K = 1 batch;
+ *   - the Ritz vectors y_i = V s_i of the nfound wanted pairs are formed by one launch (fp64 coefficients and accumulation, one
+ *     rounding to the vector dtype) and kept on the device for lam_hip_get_eigenvectors and lam_hip_eig_residuals;
+ *   - launches per step ("hip_calls_launch"): 7 -- the product and six vector launches (three-term, dots / apply twice, append) --
+ *     whatever k; 8 under option "symmetric_many", whose two-launch product the step then runs (every pair of A read once);
+ *   - refusals: what the batch refuses, with the same codes and words (several shards, rank mode, LAM_HIP_BF16); no matrix:
+ *     LAM_HIP_ESTATE; max_steps outside 1..min(N, LAM_HIP_MAX_LANCZOS), nev outside 1..max_steps, an unknown `which`:
+ *     LAM_HIP_EINVAL naming the value;
+ *   - state: its own (a basis of max_steps + 1 rows, each pitched to a 256-byte multiple of N + 16 elements and zero behind
+ *     element N so that a row is the product's input as it stands; u; the Ritz vectors; a block of scalars), allocated at the first
+ *     call, grow-only in max_steps, released with the batch.  The batch's right-hand sides and shifts are left alone; a batched or
+ *     multi-shift solution is no longer readable afterwards (LAM_HIP_ESTATE), exactly as after lam_hip_gemv_many; the single-vector
+ *     state is untouched; "multi_rhs_k" reports 1.  The eigen-solution stays readable until lam_hip_set_problem, a new matrix or the
+ *     next lam_hip_eigs.  A symmetric matrix is the caller's statement; lam_hip_check_symmetry measures it;
+ *   - out of scope: thick or implicit restart (a caller restarts by passing a combination of Ritz vectors as v0); interior
+ *     eigenvalues and shift-invert with an inner MINRES; block Lanczos on K > 1; several shards, rank mode, bf16; a selective or
+ *     partial reorthogonalisation;
+ *   - cost: per step the six vector launches move about 4 k N elements against N^2 for the product (under 1 % at N = 65536 and
+ *     256 steps); the basis takes (max_steps + 1) N elements (135 MB at N = 65536, 256 steps, fp64). */
+#define LAM_HIP_MAX_LANCZOS 256
+#define LAM_HIP_EIG_SMALLEST 0
+#define LAM_HIP_EIG_LARGEST  1
+#define LAM_HIP_EIG_BOTH     2
+int lam_hip_eigs(lam_hip_ctx *ctx, int which, int nev, int max_steps, double tol, int check_every, const void *v0_host,
+                 uint64_t seed, lam_hip_stats *stats, int32_t *nfound, double *theta, double *bound, int32_t *converged);
+/* The coefficients of the last lam_hip_eigs: *steps, alpha[steps], beta[steps] (room for LAM_HIP_MAX_LANCZOS each; any may be NULL);
+ * beta[k] is the norm that made v_{k+1}, so T_steps is (alpha[0 .. steps), beta[0 .. steps - 1)).  No eigen-solution: LAM_HIP_ESTATE. */
+int lam_hip_get_lanczos(lam_hip_ctx *ctx, int32_t *steps, double *alpha, double *beta);
+/* The first nev Ritz vectors of the last lam_hip_eigs, pair i contiguous at y_host + i*N (vector dtype), in theta's order.  More than
+ * were found: LAM_HIP_EINVAL; no eigen-solution: LAM_HIP_ESTATE. */
+int lam_hip_get_eigenvectors(lam_hip_ctx *ctx, int nev, void *y_host);
+/* res[i] = ||A y_i - theta_i y_i||_2 / ||y_i||_2 of the first nev pairs, formed on the device as lam_hip_true_residual_mshift forms
+ * its residuals: groups of up to 8 Ritz vectors through the batched product, then one pass (fp64 differences and sums).  Leaves the
+ * eigen-solution, B and X alone. */
+int lam_hip_eig_residuals(lam_hip_ctx *ctx, int nev, double *res);
+/* Host-only and context-free, like lam_hip_partition: the eigenvalues of the symmetric tridiagonal matrix with diagonal alpha[0 .. k)
+ * and off-diagonal beta[0 .. k-1) in ascending order (theta[k]), the bottom components of its eigenvectors (last_row[k], may be
+ * NULL) and, if S != NULL, the whole k x k eigenvector matrix, column i contiguous at S + i*k.  Implicit QL; without S the sweep
+ * carries the one row, O(k^2).  This is the routine lam_hip_eigs calls (csrc/lam_host_tridiag.h).  k outside
+ * 1..LAM_HIP_MAX_LANCZOS, a NULL array or a non-finite entry: LAM_HIP_EINVAL. */
+int lam_hip_tridiag_eigen(int k, const double *alpha, const double *beta, double *theta, double *last_row, double *S);
+
 /* ---- single operators (reference private members / CUDA kernels, for parity tests, roofline
  *      probes and callers that want the BLAS pieces) ------------------------------------------ */
 
@@ -470,6 +541,11 @@ int lam_hip_gemv_only(lam_hip_ctx *ctx, int reps, double *sec_per_gemv);
 int lam_hip_dot(lam_hip_ctx *ctx, const void *x_host, const void *y_host, uint64_t n, double *result);
 int lam_hip_axpby(lam_hip_ctx *ctx, double alpha, const void *x_host, double beta, void *y_host,
                   uint64_t n);
+/* The reorthogonalisation pass of lam_hip_eigs alone, ONE pass with the kernels the solve uses, on host vectors; needs no problem
+ * and no matrix.  V_host: m vectors of n elements (vector dtype), vector j at V_host + j*n, 1 <= m <= LAM_HIP_MAX_LANCZOS.
+ * coeff[j] = V_j.u with fp64 sums of fixed order (may be NULL); then u -= sum_j (TV)coeff[j] V_j as an fma chain in ascending j,
+ * written back to u_host.  Columns do not mix in the coefficients: a NaN in V_j reaches coeff[j] and u, and no other coeff. */
+int lam_hip_project_out(lam_hip_ctx *ctx, uint64_t n, int m, const void *V_host, void *u_host, double *coeff);
 
 /* max |A[i][j] - A[j][i]| of the matrix held by a single-PROCESS context (one shard or several; every storage type): lets a
  * caller verify the precondition of option "symmetric".  Exact: the fp64 difference of the two stored values, no tolerance.
