@@ -27,6 +27,17 @@ constexpr int64_t kRankModeDefaultExchange = 1;      // lam_hip_create_rank (rou
 constexpr int64_t kOneProcessDefaultExchange = 1;    // lam_hip_create with several shards
 constexpr int kVecBlocksMax = 256;
 
+// A plan of the symmetric product (lam_host_plan.h, symv_plan) on the device with the partials of its two passes (symv_dev_build
+// below): one per shard for the single product (ShardBase::symv), the batch's own (MultiState::sym).
+struct SymvDevPlan {
+    SymvTask *tasks = nullptr;            // null: not built
+    uint32_t *index = nullptr;            // what the second pass needs to find the partials (lam_host_plan.h, SymvIndex)
+    SymvIndex ix = {};
+    int ntasks = 0;
+    uint64_t rowpart_elems = 0;           // row partials per column of p
+    void *rowpart = nullptr, *colpart = nullptr;
+};
+
 struct ShardBase {
     int dev = 0;
     int index = 0;               // global shard index
@@ -46,11 +57,7 @@ struct ShardBase {
                                  // their peers' buffers themselves and a shard may start the next GEMV while a slower peer is
                                  // still reading this iteration's records (ap_gather_bytes = one buffer)
     size_t ap_gather_bytes = 0;
-    void *symv_rowpart = nullptr, *symv_colpart = nullptr;   // symmetric product (option "symmetric")
-    SymvTask *symv_tasks = nullptr;
-    uint32_t *symv_index = nullptr;       // what the second pass needs to find the partials (lam_kernels.h, SymvIndex)
-    SymvIndex symv_ix = {};
-    int symv_ntasks = 0;
+    SymvDevPlan symv;                     // symmetric product (option "symmetric"): the shard's plan and partials, built at first use
     void *symv_gather = nullptr;          // several shards: P records [full-length contribution to A p | double], double-buffered
                                           // like ap_gather in one process (symv_gather_bytes = one buffer)
     size_t symv_gather_bytes = 0;
@@ -148,14 +155,10 @@ struct MultiState {
     MshiftState ms;
     MinresState mr;
     // symmetric batched product (option "symmetric_many", multi_sym_ensure): the batch's own plan and partials, nothing shared with
-    // ShardBase::symv_*.  The plan is built at first use for the batch's n and the storage's vector width (sym_vec); the partials are
+    // ShardBase::symv.  The plan is built at first use for the batch's n and the storage's vector width (sym_vec); the partials are
     // K-wide records and grow-only in K (sym_cap_K); released with the batch.
-    SymvTask *sym_tasks = nullptr;
-    uint32_t *sym_index = nullptr;
-    SymvIndex sym_ix = {};
-    int sym_ntasks = 0, sym_vec = 0, sym_cap_K = 0;
-    uint64_t sym_rowpart_elems = 0;      // per column
-    void *sym_rowpart = nullptr, *sym_colpart = nullptr;
+    SymvDevPlan sym;
+    int sym_vec = 0, sym_cap_K = 0;
 };
 
 // Jacobi preconditioner of the batched solve (lam_hip_solve_many_pc, lam_multi.h): the diagonal of the matrix and its reciprocal,
@@ -433,6 +436,53 @@ struct PinnedBuf {
     void *p = nullptr;
     ~PinnedBuf() { if (p) (void)hipHostFree(p); }
 };
+
+void symv_dev_release(SymvDevPlan &d)
+{
+    for (void *q : {(void *)d.tasks, (void *)d.index, d.rowpart, d.colpart}) if (q) (void)hipFree(q);
+    d = SymvDevPlan();
+}
+
+// The partials of `d` for K columns of p (K-wide records of `esz` bytes an element), in place of the ones it holds; both or neither.
+// Columns behind the end of a ragged strip are never written by a task: the second pass does not read them either.
+int symv_dev_partials(lam_hip_ctx *c, SymvDevPlan &d, uint64_t SS, size_t esz, int K, hipStream_t stream)
+{
+    const size_t rbytes = (size_t)d.rowpart_elems * K * esz, cbytes = (size_t)d.ntasks * SS * K * esz;
+    DevBuf rp, cp;
+    HIPCHK(c, hipMalloc(&rp.p, rbytes));
+    HIPCHK(c, hipMalloc(&cp.p, cbytes));
+    HIPCHK(c, hipMemsetAsync(cp.p, 0, cbytes, stream));
+    if (d.rowpart != nullptr) HIPCHK(c, hipStreamSynchronize(stream));     // no launch on the smaller buffers is in flight
+    for (void *q : {d.rowpart, d.colpart}) if (q) (void)hipFree(q);
+    d.rowpart = rp.p; d.colpart = cp.p;
+    rp.p = cp.p = nullptr;
+    return 0;
+}
+
+// The one place a plan goes to the device: symv_plan for rows [row0, row0 + nrows) in strips of SS columns (cyc: the cyclic half
+// windows of several row shards), its tasks and index, the partials for K columns.  All or nothing: a failure leaves `d` unbuilt.
+int symv_dev_build(lam_hip_ctx *c, SymvDevPlan &d, uint64_t n, uint64_t ncv, uint64_t SS, uint64_t row0, uint64_t nrows, bool cyc,
+                   size_t esz, int K, hipStream_t stream, const char *what)
+{
+    SymvPlan plan;
+    symv_plan(n, ncv, SS, row0, nrows, cyc, &plan);
+    if (plan.tasks.empty()) return fail(c, LAM_HIP_EINVAL, "%s: no tasks", what);
+    if (plan.rowpart_elems >> 32) return fail(c, LAM_HIP_EINVAL, "%s: too many row partials for 32-bit offsets", what);
+    DevBuf t, sb;
+    HIPCHK(c, hipMalloc(&t.p, plan.tasks.size() * sizeof(SymvTask)));
+    HIPCHK(c, hipMalloc(&sb.p, plan.index.size() * sizeof(uint32_t)));
+    HIPCHK(c, hipMemcpy(t.p, plan.tasks.data(), plan.tasks.size() * sizeof(SymvTask), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(sb.p, plan.index.data(), plan.index.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SymvDevPlan b;
+    b.ix = plan.ix;
+    b.ntasks = (int)plan.tasks.size();
+    b.rowpart_elems = plan.rowpart_elems;
+    LAMCHK(symv_dev_partials(c, b, SS, esz, K, stream));
+    b.tasks = t.as<SymvTask>(); b.index = sb.as<uint32_t>();
+    t.p = sb.p = nullptr;
+    d = b;
+    return 0;
+}
 
 int vec_grid(uint64_t n_loc)
 {

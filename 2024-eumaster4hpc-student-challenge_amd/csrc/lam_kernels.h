@@ -31,7 +31,8 @@
 //     accumulate, which is how the rank mode overlaps the all-gather of p with its own-slice panel.
 //   * the *_full_kernel family implements the single-exchange iteration (gather of Ap, full-length r and p on every shard);
 //     symv_*_kernel implement the opt-in symmetric product (every pair {i, j} read once: the upper triangle on one shard,
-//     cyclic half windows on several row shards); symv_many_*_kernel are its K-wide form for the batch (option "symmetric_many").
+//     cyclic half windows on several row shards); symv_many_*_kernel are the batch's entry points into the same two bodies (option
+//     "symmetric_many", K interleaved columns).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -1054,9 +1055,14 @@ gemv_mfma_bf16_kernel(GemvArgs<__hip_bfloat16, float> a)
 // CG needs A symmetric positive definite, so A[i][j] (j > i) can serve both y_i += A_ij p_j and
 // y_j += A_ij p_i: 17.2 GB per product instead of 34.4 GB at N=65536 fp64 -- the only way past the
 // HBM roofline of the plain GEMV.  Two passes (round 4: second shape; the round-1 shape flushed a column
-// partial per 32 rows -- 0.55 GB written and read again per product -- and kept 32 row partials per lane):
-//   symv_task_kernel    one workgroup per TASK = a column strip (NV x 4 KiB per row, read contiguously by the
-//                       4 waves; the product uses NV = 1: 512 fp64 / 1024 fp32 columns) x a run of rows (2048 for the
+// partial per 32 rows -- 0.55 GB written and read again per product -- and kept 32 row partials per lane).  The second pass is ONE body
+// (symv_reduce_body: K interleaved columns of p) with two entry points: symv_reduce_kernel is its K = 1 case for one vector, on one
+// shard or several, symv_many_reduce_kernel ("Symmetric batched product" below) serves the batch.  The first pass is still written
+// twice (symv_task_kernel here, symv_many_task_kernel below): run through the batch's statements the single product measured 1-2 %
+// slower at N = 65536 ... 131072 (profiles/symv_unified_parent_vs_branch.txt).
+//   symv_task_kernel    one workgroup per TASK = a column strip (4 KiB per row, read contiguously by the
+//                       4 waves: 512 fp64 / 1024 fp32 columns; two vectors per lane ran level or 2-5 % behind,
+//                       profiles/r04_symv2_probe.txt, and are no longer instantiated: NV = 1) x a run of rows (2048 for the
 //                       bulk of the triangle, 512 from 60 % of the work on, 64 for the last 8 %, so that the launch
 //                       ends on short tasks; shorter runs for small N).  A lane keeps the column partials of its
 //                       columns in registers over ALL rows of the task and 8 row partials at a time: every 8 rows they
@@ -1132,14 +1138,16 @@ __device__ __forceinline__ T wave_sum8(const T (&v)[8])
 // CU: the tasks' loads alone run at 7.22 TB/s with three workgroups per CU against 7.0 with the five its registers allow, the
 // whole pass 1-2 % faster (fewer row streams in flight at a time; profiles/r04_symv2_probe.txt).
 constexpr unsigned kSymvLdsPerWorkgroup = 53 * 1024;
-template <typename T> constexpr unsigned symv_lds_pad() { return kSymvLdsPerWorkgroup - (unsigned)sizeof(T) * kWaves * kSymvRowsLds; }   // T: vector type
-template <typename TA, typename T, int NV, bool CYC>     // TA: storage of the matrix; T: vectors, products, partials (bf16 storage: float)
+template <typename T, int K> constexpr unsigned symv_lds_pad() { return kSymvLdsPerWorkgroup - (unsigned)sizeof(T) * kWaves * kSymvRowsLds * K; }   // T: vector type
+
+template <typename TA, typename T, bool CYC>     // TA: storage of the matrix; T: vectors, products, partials (bf16 storage: float)
 __global__ void __launch_bounds__(kBlock)
 symv_task_kernel(const TA *__restrict__ A, const T *__restrict__ p, const SymvTask *__restrict__ tasks, T *__restrict__ rowpart,
                  T *__restrict__ colpart, uint64_t lda, uint64_t ncols_vec, uint64_t n, uint64_t row_off, const CgScalars *sc)
 {
     using MV = MatVec<TA>;
     using vec_t = typename MV::vec_t;                                // 16 bytes of matrix elements
+    constexpr int NV = 1;                                            // 16-byte vectors per lane and row: two ran level or behind (profiles/r04_symv2_probe.txt)
     constexpr int VEC = MV::N, CW = kBlock * VEC, SS = NV * CW;     // CW: columns the workgroup covers with one vector per lane
     typedef T tvec_t __attribute__((ext_vector_type(VEC)));          // the same columns of a vector / a column partial
     __shared__ T s_rows[kWaves][kSymvRowsLds];
@@ -1299,47 +1307,50 @@ symv_task_kernel(const TA *__restrict__ A, const T *__restrict__ p, const SymvTa
         }
 }
 
-// Second pass.  32 entries of y per workgroup; the terms of an entry are dealt round-robin to 8 groups of 32 lanes and combined
-// in a fixed order.  Both kinds of partial are indexed BY TASK, in dispatch order -- rowpart[task][row of the run],
-// colpart[task][column of the strip] --, so that the tasks in flight together write next to each other: with the partials
-// laid out by strip (a 4-KiB column partial every ~1 MiB, a 2-KiB row partial every 512 KiB) the first pass ran up to 10 %
-// slower depending on where the buffers happened to be placed (2.57 ... 2.85 ms for the same launch at N=65536; with every task
-// writing ONE slot 2.52 ... 2.61: profiles/r04_symv2_probe.txt) -- 1 % of the traffic, but scattered over as many pages as
-// tasks.  Row side: the tasks of the row's run (consecutive) for the rows this shard owns, [row_off, row_off + nloc); column
-// side: the tasks listed for the column's strip.  One shard: y is the product, `partial` its p.y per workgroup.  Several shards
-// (dst.n > 0): the entry is this shard's CONTRIBUTION to y[i], stored into its record in every shard's gather buffer; the
-// consumer adds the shards' records in shard order; the launch carries one extra workgroup (fin.active) that sums the
-// workgroups' parts of p.Ap in the fixed order of block_sum_array and writes the total behind the record (see Finalize).
-template <typename T, int SS>         // T: vectors and partials; SS: columns of a strip
-__global__ void __launch_bounds__(kBlock)
-symv_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart, const uint32_t *__restrict__ index, SymvIndex ix,
-                   const T *__restrict__ p, T *__restrict__ y, double *__restrict__ partial, uint64_t n, uint64_t row_off,
-                   uint64_t nloc, PtrList dst, Finalize fin, const CgScalars *sc)
+// Second pass, written once for both entry points too.  32 rows of y per workgroup, K accumulators per thread; the terms of an
+// entry are dealt round-robin to 8 groups of 32 lanes and combined in a fixed order, the same for every column.  Both kinds of
+// partial are indexed BY TASK, in dispatch order -- rowpart[task][row of the run], colpart[task][column of the strip] --, so that
+// the tasks in flight together write next to each other: with the partials laid out by strip (a 4-KiB column partial every ~1 MiB,
+// a 2-KiB row partial every 512 KiB) the first pass ran up to 10 % slower depending on where the buffers happened to be placed
+// (2.57 ... 2.85 ms for the same launch at N=65536; with every task writing ONE slot 2.52 ... 2.61: profiles/r04_symv2_probe.txt)
+// -- 1 % of the traffic, but scattered over as many pages as tasks.  Row side: the tasks of the row's run (consecutive) for the rows
+// this shard owns, [row_off, row_off + nloc); column side: the tasks listed for the column's strip.  The epilogue has one thread per
+// (row, column), element e = row * K + j of the workgroup: SHIFT adds shift[j] p_j[row] with one fma, store(global element, value)
+// puts the entry where the entry point wants it, and -- want_dot -- publish(j, d) takes the workgroup's partial d of p_j.y_j, the 32
+// terms summed in row order.  s_dot is the caller's (the single entry point's reducer workgroup uses it as well).
+template <typename T, int SS, int K, bool SHIFT, typename Store, typename Publish>         // T: vectors and partials; SS: columns of a strip
+__device__ __forceinline__ void
+symv_reduce_body(const T *__restrict__ rowpart, const T *__restrict__ colpart, const uint32_t *__restrict__ index, const SymvIndex &ix,
+                 const T *__restrict__ p, uint64_t n, uint64_t row_off, uint64_t nloc, const T *shift, double (&s_dot)[K][kSymvReduceRows],
+                 bool want_dot, Store store, Publish publish)
 {
     constexpr int RB = kSymvReduceRows, G = kBlock / RB;
-    __shared__ T s[G][RB];
-    __shared__ double s_dot[RB];
+    static_assert(RB * K <= kBlock, "one epilogue thread per (row, column)");
+    __shared__ T s[G][RB * K];
     __shared__ uint32_t s_list[kSymvListChunk];
-    if (sc != nullptr && sc->stop) return;
-    if (is_reducer_block(fin)) {                        // several shards: the shard's part of p.Ap as ONE number, inside this launch
-        reduce_partials(partial, (int)compute_blocks(fin), fin, s_dot);
-        return;
-    }
     const int l = threadIdx.x % RB, g = threadIdx.x / RB;
     const uint64_t i = (uint64_t)blockIdx.x * RB + l;
-    T acc = (T)0;
+    T acc[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = (T)0;
     if (i < n && i >= row_off && i < row_off + nloc) {
         const uint64_t il = i - row_off;
         const uint32_t *run = index + ix.runs + 5 * index[ix.row8 + (il >> 3)];
         const uint32_t cnt = run[1], h = run[3];
-        const T *src = rowpart + (uint64_t)run[4] + (il - run[2]);
+        const T *src = rowpart + ((uint64_t)run[4] + (il - run[2])) * K;
+        const uint64_t hk = (uint64_t)h * K;
         uint32_t q = g;
         for (; q + 3 * G < cnt; q += 4 * G) {
-            const T a0 = src[(uint64_t)q * h], a1 = src[(uint64_t)(q + G) * h];
-            const T a2 = src[(uint64_t)(q + 2 * G) * h], a3 = src[(uint64_t)(q + 3 * G) * h];
-            acc += (a0 + a1) + (a2 + a3);
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const T a0 = src[(uint64_t)q * hk + j], a1 = src[(uint64_t)(q + G) * hk + j];
+                const T a2 = src[(uint64_t)(q + 2 * G) * hk + j], a3 = src[(uint64_t)(q + 3 * G) * hk + j];
+                acc[j] += (a0 + a1) + (a2 + a3);
+            }
         }
-        for (; q < cnt; q += G) acc += src[(uint64_t)q * h];
+        for (; q < cnt; q += G)
+#pragma unroll
+            for (int j = 0; j < K; j++) acc[j] += src[(uint64_t)q * hk + j];
     }
     // column side: the workgroup's 32 columns lie in ONE strip (32 divides the strip width), so its task list is staged in LDS
     // once per 1024 entries -- a load of the list in front of every load of a partial doubled the chain of memory latencies that
@@ -1348,7 +1359,8 @@ symv_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart,
         const uint32_t s0 = (uint32_t)(((uint64_t)blockIdx.x * RB) / SS);
         const uint32_t lb = index[ix.strip_base + s0], le = index[ix.strip_base + s0 + 1];
         const uint32_t *list = index + ix.strip_tasks;
-        const T *src = colpart + (i - (uint64_t)s0 * SS);
+        const T *src = colpart + (i - (uint64_t)s0 * SS) * K;
+        constexpr uint64_t SK = (uint64_t)SS * K;
         for (uint32_t base = lb; base < le; base += kSymvListChunk) {
             const uint32_t cnt = le - base < (uint32_t)kSymvListChunk ? le - base : (uint32_t)kSymvListChunk;
             __syncthreads();                                  // the previous chunk has been consumed
@@ -1357,34 +1369,72 @@ symv_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart,
             if (i < n) {
                 uint32_t k = g;
                 for (; k + 7 * G < cnt; k += 8 * G) {
-                    T a[8];
 #pragma unroll
-                    for (int u = 0; u < 8; u++) a[u] = src[(uint64_t)s_list[k + u * G] * SS];
-                    acc += ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+                    for (int j = 0; j < K; j++) {
+                        T a[8];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) a[u] = src[(uint64_t)s_list[k + u * G] * SK + j];
+                        acc[j] += ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+                    }
                 }
-                for (; k < cnt; k += G) acc += src[(uint64_t)s_list[k] * SS];
+                for (; k < cnt; k += G)
+#pragma unroll
+                    for (int j = 0; j < K; j++) acc[j] += src[(uint64_t)s_list[k] * SK + j];
             }
         }
     }
-    s[g][l] = acc;
-    __syncthreads();
-    if (g == 0) {
-        T t = s[0][l];
 #pragma unroll
-        for (int k = 1; k < G; k++) t += s[k][l];
-        if (i < n) {
+    for (int j = 0; j < K; j++) s[g][l * K + j] = acc[j];
+    __syncthreads();
+    if (threadIdx.x < RB * K) {
+        const int e = threadIdx.x, row = e / K, j = e % K;
+        const uint64_t ir = (uint64_t)blockIdx.x * RB + row;
+        T t = s[0][e];
+#pragma unroll
+        for (int k = 1; k < G; k++) t += s[k][e];
+        double d = 0.0;
+        if (ir < n) {
+            const T pj = p[ir * K + j];
+            if constexpr (SHIFT) t = fma_tv(shift[j], pj, t);
+            store(ir * K + j, t);
+            d = (double)t * (double)pj;
+        }
+        s_dot[j][row] = d;
+    }
+    if (want_dot) {
+        __syncthreads();
+        if (threadIdx.x < K) {
+            double d = 0.0;
+#pragma unroll
+            for (int k = 0; k < RB; k++) d += s_dot[threadIdx.x][k];
+            publish((int)threadIdx.x, d);
+        }
+    }
+}
+
+// The single product's second pass.  One shard: y is the product, `partial` its p.y per workgroup.  Several shards (dst.n > 0): the
+// entry is this shard's CONTRIBUTION to y[i] (row-side partials only for the rows it owns), stored into its record in every shard's
+// gather buffer; the consumer adds the shards' records in shard order; the launch carries one extra workgroup (fin.active) that sums
+// the workgroups' parts of p.Ap in the fixed order of block_sum_array and writes the total behind the record (see Finalize).
+template <typename T, int SS>
+__global__ void __launch_bounds__(kBlock)
+symv_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart, const uint32_t *__restrict__ index, SymvIndex ix,
+                   const T *__restrict__ p, T *__restrict__ y, double *__restrict__ partial, uint64_t n, uint64_t row_off,
+                   uint64_t nloc, PtrList dst, Finalize fin, const CgScalars *sc)
+{
+    __shared__ double s_dot[1][kSymvReduceRows];
+    if (sc != nullptr && sc->stop) return;
+    if (is_reducer_block(fin)) {                        // several shards: the shard's part of p.Ap as ONE number, inside this launch
+        reduce_partials(partial, (int)compute_blocks(fin), fin, s_dot[0]);
+        return;
+    }
+    symv_reduce_body<T, SS, 1, false>(
+        rowpart, colpart, index, ix, p, n, row_off, nloc, (const T *)nullptr, s_dot, partial != nullptr,
+        [&](uint64_t i, T t) {
             if (dst.n == 0) y[i] = t;
             else for (int j = 0; j < dst.n; j++) reinterpret_cast<T *>(dst.p[j])[i] = t;
-        }
-        s_dot[l] = i < n ? (double)t * (double)p[i] : 0.0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && partial != nullptr) {
-        double d = 0.0;
-#pragma unroll
-        for (int k = 0; k < RB; k++) d += s_dot[k];
-        publish_partial(d, partial, fin);               // plain store, or the self-flagging slot the reducer workgroup waits for
-    }
+        },
+        [&](int, double d) { publish_partial(d, partial, fin); });   // plain store, or the self-flagging slot the reducer workgroup waits for
 }
 
 // The asymmetry of the matrix one process holds, over every pair {A[i][j], A[j][i]}; three per-workgroup maxima, in out[blockIdx.x],
@@ -2622,16 +2672,17 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
 
 // Symmetric batched product (option "symmetric_many", lam_multi.h multi_launch_gemv): Y = A P for K = 1, 2, 4 interleaved columns
 // reading every pair {A_ij, A_ji} once -- the two passes of the single symmetric product ("Symmetric product" above: one shard, the
-// upper triangle, NV = 1, the plan of symv_plan unchanged) with K of everything a lane keeps per column of P: its p values, its column
-// partials, its 8 row partials.  The matrix loads, the tasks, the lean / masked / ragged loops and the use rule are the single path's;
-// so is, statement for statement, the order of every sum of column j: column j of Y is bit for bit what symv_task_kernel +
-// symv_reduce_kernel give for that vector alone, whatever K is and whatever the other columns hold.
+// upper triangle, the plan of symv_plan unchanged) with K of everything a lane keeps per column of P: its p values, its column
+// partials, its 8 row partials.  The first pass is a statement-for-statement copy of symv_task_kernel with a K loop around those (the
+// matrix loads, the tasks, the lean / masked / ragged loops and the use rule are the single path's); the second pass is the single
+// path's own body, symv_reduce_body.  The order of every sum of column j is the single path's: column j of Y is bit for bit what
+// symv_task_kernel + symv_reduce_kernel give for that vector alone, whatever K is and whatever the other columns hold
+// (tests/test_gpu_symmetric_many.py), and tests/test_gpu_symmetric_bits.py pins both against a recorded build.
 // Partials are K-wide records: rowpart[(rp + row) * K + j], colpart[(task * SS + column) * K + j] (64-bit offsets: the products with K
 // pass 2^32).  The LDS row buffer is K-wide too (fp64 K = 4: 32 KiB); the idle dynamic LDS behind it keeps the launch at three
-// workgroups per CU as in the single path.
+// workgroups per CU as in the single path (symv_lds_pad<T, K>).
 constexpr int kSymvManyMaxK = 4;       // K = 8 stays on the general product (staging- and barrier-bound, not byte-bound: DESIGN §8)
 template <typename T> struct ShiftArg { T s[kSymvManyMaxK]; };       // SHIFT only: s_j of Y_j = (A + s_j I) P_j, by value
-template <typename T, int K> constexpr unsigned symv_many_lds_pad() { return kSymvLdsPerWorkgroup - (unsigned)sizeof(T) * kWaves * kSymvRowsLds * K; }
 template <typename TA, typename T, int K>
 __global__ void __launch_bounds__(kBlock)
 symv_many_task_kernel(const TA *__restrict__ A, const T *__restrict__ p, const SymvTask *__restrict__ tasks, T *__restrict__ rowpart,
@@ -2789,100 +2840,19 @@ symv_many_task_kernel(const TA *__restrict__ A, const T *__restrict__ p, const S
     }
 }
 
-// Second pass of the symmetric batched product: symv_reduce_kernel (one shard) with K accumulators per thread -- 32 rows per
-// workgroup, the same fixed order of the row-run terms and of the strip's task list for every column.  The epilogue has one thread per
-// (row, column), as multi_gemv_kernel's: SHIFT adds s_j p_j[row] with one fma, y[row * K + j] is stored, and the workgroup's
-// p_j.(A p_j) partial goes to partial[j * gridDim.x + block] (gridDim.x = ceil(n / 32): what the batch's consumers are told).
+// Second pass of the batch: every row is the one shard's, y[row * K + j] is stored plainly, and the workgroup's p_j.(A p_j) partial goes
+// to partial[j * gridDim.x + block] (gridDim.x = ceil(n / 32): what the batch's consumers are told).
 template <typename T, int SS, int K, bool SHIFT>
 __global__ void __launch_bounds__(kBlock)
 symv_many_reduce_kernel(const T *__restrict__ rowpart, const T *__restrict__ colpart, const uint32_t *__restrict__ index, SymvIndex ix,
                         const T *__restrict__ p, T *__restrict__ y, double *__restrict__ partial, uint64_t n, ShiftArg<T> shift,
                         const MultiScalars *sc)
 {
-    constexpr int RB = kSymvReduceRows, G = kBlock / RB;
-    static_assert(RB * K <= kBlock, "one epilogue thread per (row, column)");
-    __shared__ T s[G][RB * K];
-    __shared__ double s_dot[K][RB];
-    __shared__ uint32_t s_list[kSymvListChunk];
+    __shared__ double s_dot[K][kSymvReduceRows];
     if (sc != nullptr && sc->all_stop) return;
-    const int l = threadIdx.x % RB, g = threadIdx.x / RB;
-    const uint64_t i = (uint64_t)blockIdx.x * RB + l;
-    T acc[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) acc[j] = (T)0;
-    if (i < n) {
-        const uint32_t *run = index + ix.runs + 5 * index[ix.row8 + (i >> 3)];
-        const uint32_t cnt = run[1], h = run[3];
-        const T *src = rowpart + ((uint64_t)run[4] + (i - run[2])) * K;
-        const uint64_t hk = (uint64_t)h * K;
-        uint32_t q = g;
-        for (; q + 3 * G < cnt; q += 4 * G) {
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-                const T a0 = src[(uint64_t)q * hk + j], a1 = src[(uint64_t)(q + G) * hk + j];
-                const T a2 = src[(uint64_t)(q + 2 * G) * hk + j], a3 = src[(uint64_t)(q + 3 * G) * hk + j];
-                acc[j] += (a0 + a1) + (a2 + a3);
-            }
-        }
-        for (; q < cnt; q += G)
-#pragma unroll
-            for (int j = 0; j < K; j++) acc[j] += src[(uint64_t)q * hk + j];
-    }
-    {
-        const uint32_t s0 = (uint32_t)(((uint64_t)blockIdx.x * RB) / SS);
-        const uint32_t lb = index[ix.strip_base + s0], le = index[ix.strip_base + s0 + 1];
-        const uint32_t *list = index + ix.strip_tasks;
-        const T *src = colpart + (i - (uint64_t)s0 * SS) * K;
-        constexpr uint64_t SK = (uint64_t)SS * K;
-        for (uint32_t base = lb; base < le; base += kSymvListChunk) {
-            const uint32_t cnt = le - base < (uint32_t)kSymvListChunk ? le - base : (uint32_t)kSymvListChunk;
-            __syncthreads();                                  // the previous chunk has been consumed
-            for (uint32_t q = threadIdx.x; q < cnt; q += kBlock) s_list[q] = list[base + q];
-            __syncthreads();
-            if (i < n) {
-                uint32_t k = g;
-                for (; k + 7 * G < cnt; k += 8 * G) {
-#pragma unroll
-                    for (int j = 0; j < K; j++) {
-                        T a[8];
-#pragma unroll
-                        for (int u = 0; u < 8; u++) a[u] = src[(uint64_t)s_list[k + u * G] * SK + j];
-                        acc[j] += ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-                    }
-                }
-                for (; k < cnt; k += G)
-#pragma unroll
-                    for (int j = 0; j < K; j++) acc[j] += src[(uint64_t)s_list[k] * SK + j];
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < K; j++) s[g][l * K + j] = acc[j];
-    __syncthreads();
-    if (threadIdx.x < RB * K) {
-        const int e = threadIdx.x, row = e / K, j = e % K;
-        const uint64_t ir = (uint64_t)blockIdx.x * RB + row;
-        T t = s[0][e];
-#pragma unroll
-        for (int k = 1; k < G; k++) t += s[k][e];
-        double d = 0.0;
-        if (ir < n) {
-            const T pj = p[ir * K + j];
-            if constexpr (SHIFT) t = fma_tv(shift.s[j], pj, t);
-            y[ir * K + j] = t;
-            d = (double)t * (double)pj;
-        }
-        s_dot[j][row] = d;
-    }
-    if (partial != nullptr) {
-        __syncthreads();
-        if (threadIdx.x < K) {
-            double d = 0.0;
-#pragma unroll
-            for (int k = 0; k < RB; k++) d += s_dot[threadIdx.x][k];
-            partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = d;
-        }
-    }
+    symv_reduce_body<T, SS, K, SHIFT>(
+        rowpart, colpart, index, ix, p, n, 0, n, shift.s, s_dot, partial != nullptr, [&](uint64_t e, T t) { y[e] = t; },
+        [&](int j, double d) { partial[(size_t)j * gridDim.x + blockIdx.x] = d; });
 }
 
 // X = 0, R = B, P = B (PC: dinv o B); per-workgroup partials of b_j.b_j (PC: and of r_j.z_j = b_j.(dinv o b_j)), both at

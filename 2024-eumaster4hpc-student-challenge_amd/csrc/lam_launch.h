@@ -71,7 +71,7 @@ struct Impl {
         const char *ta = sizeof(TA) == 8 ? "double" : (sizeof(TA) == 4 ? "float" : "__hip_bfloat16");
         const char *tv = sizeof(TV) == 8 ? "double" : "float";
         char buf[192];
-        if (c->symv_active()) { snprintf(buf, sizeof buf, "symv_task_kernel<%s,NV=%d> + symv_reduce_kernel<%s,NV=%d>", ta, symv_nv(c), ta, symv_nv(c)); return buf; }
+        if (c->symv_active()) { snprintf(buf, sizeof buf, "symv_task_kernel<%s,NV=1> + symv_reduce_kernel<%s,NV=1>", ta, ta); return buf; }
         if (!fast_ok(c)) { snprintf(buf, sizeof buf, "gemv_generic_kernel<%s,%s>", ta, tv); return buf; }
         const int v = variant(c);
         const char *nt = c->opt_nt ? "true" : "false";
@@ -132,68 +132,32 @@ struct Impl {
     // by first row, strips of one row run side by side (whole rows stream, as in the GEMV).  Shapes from tools/symv2_probe
     // (profiles/r04_symv2_probe.txt): one 16-byte vector per lane and row (a 4-KiB strip per workgroup); one shard: tall = 256
     // rows from N = 16384 on; several: tall so that a shard has >= ~6000 tasks.
-    template <int NV>
-    static int build_symv_tasks(lam_hip_ctx *c, ShardBase &s, bool cyc)
-    {
-        const uint64_t n = c->n, SS = (uint64_t)NV * kBlock * VEC, ncv = c->ncols_vec();
-        SymvPlan plan;
-        symv_plan(n, ncv, SS, s.row0, s.nrows, cyc, &plan);
-        const std::vector<SymvTask> &tasks = plan.tasks;
-        if (tasks.empty()) return fail(c, LAM_HIP_EINVAL, "symmetric product: no tasks");
-        // all four or none: a later failure must not leave the earlier buffers behind
-        DevBuf t, rp, cp, sb;
-        HIPCHK(c, hipMalloc(&t.p, tasks.size() * sizeof(SymvTask)));
-        if (plan.rowpart_elems >> 32) return fail(c, LAM_HIP_EINVAL, "symmetric product: too many row partials for 32-bit offsets");
-        HIPCHK(c, hipMalloc(&rp.p, (size_t)plan.rowpart_elems * sizeof(TV)));
-        HIPCHK(c, hipMalloc(&cp.p, tasks.size() * SS * sizeof(TV)));
-        HIPCHK(c, hipMalloc(&sb.p, plan.index.size() * sizeof(uint32_t)));
-        HIPCHK(c, hipMemcpy(t.p, tasks.data(), tasks.size() * sizeof(SymvTask), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(sb.p, plan.index.data(), plan.index.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        // columns behind the end of a ragged strip are never written by a task: the second pass does not read them either
-        HIPCHK(c, hipMemsetAsync(cp.p, 0, tasks.size() * SS * sizeof(TV), s.stream));
-        s.symv_tasks = t.as<SymvTask>(); s.symv_rowpart = rp.p; s.symv_colpart = cp.p; s.symv_index = sb.as<uint32_t>();
-        s.symv_ix = plan.ix;
-        t.p = rp.p = cp.p = sb.p = nullptr;
-        s.symv_ntasks = (int)tasks.size();
-        return 0;
-    }
-    // the two passes.  dst.n == 0: one shard, y = A p and `partial` = the p.y partials (symv_reduce_grid(n) of them).  dst.n > 0:
-    // several shards, the shard's full-length contribution goes into dst.p[] (its record in every shard's gather buffer).
-    template <int NV>
-    static int launch_symv_nv(lam_hip_ctx *c, ShardBase &s, const TV *p, TV *y, double *partial, const CgScalars *sc, const PtrList &dst,
-                              const Finalize &fin)
-    {
-        const bool cyc = dst.n > 0;
-        const uint64_t n = c->n, ncv = c->ncols_vec();
-        if (s.symv_tasks == nullptr) LAMCHK(build_symv_tasks<NV>(c, s, cyc));
-        if (cyc)
-            hipLaunchKernelGGL((symv_task_kernel<TA, TV, NV, true>), dim3(s.symv_ntasks), dim3(kBlock), symv_lds_pad<TV>(), s.stream, (const TA *)s.A, p,
-                               (const SymvTask *)s.symv_tasks, (TV *)s.symv_rowpart, (TV *)s.symv_colpart, c->lda, ncv, n, s.row0, sc);
-        else
-            hipLaunchKernelGGL((symv_task_kernel<TA, TV, NV, false>), dim3(s.symv_ntasks), dim3(kBlock), symv_lds_pad<TV>(), s.stream, (const TA *)s.A, p,
-                               (const SymvTask *)s.symv_tasks, (TV *)s.symv_rowpart, (TV *)s.symv_colpart, c->lda, ncv, n, s.row0, sc);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL((symv_reduce_kernel<TV, NV * kBlock * VEC>), dim3(symv_reduce_grid(n) + (fin.active ? 1 : 0)), dim3(kBlock), 0, s.stream,
-                           (const TV *)s.symv_rowpart, (const TV *)s.symv_colpart, (const uint32_t *)s.symv_index, s.symv_ix, p, y,
-                           partial, n, s.row0, s.nrows, dst, fin, sc);
-        HIPCHK(c, hipGetLastError());
-        c->n_launch += 2;
-        return 0;
-    }
+    // The two passes.  dst null: one shard, y = A p and `partial` = the p.y partials (symv_reduce_grid(n) of them).  dst set:
+    // several shards, the shard's full-length contribution goes into dst->p[] (its record in every shard's gather buffer), and `fin`
+    // says where the reducer workgroup of the second pass writes the shard's part of p.Ap.
     static int symv_reduce_grid(uint64_t n) { return (int)((n + kSymvReduceRows - 1) / kSymvReduceRows); }
-    // vectors per lane and row: one everywhere -- with the pipelined interior loop one 4-KiB strip per workgroup runs level with
-    // two at N = 65536 (fp64) / 131072 (fp32) and 2-5 % ahead at N <= 40000 (profiles/r04_symv2_probe.txt); two stays compiled
-    static int symv_nv(const lam_hip_ctx *) { return 1; }
-    // `fin` (several shards): where the reducer workgroup of the second pass writes the shard's part of p.Ap
     static int launch_symv(lam_hip_ctx *c, ShardBase &s, const TV *p, TV *y, double *partial, const CgScalars *sc, const PtrList *dst = nullptr,
                            const Finalize *fin = nullptr)
     {
-        PtrList none;
-        none.n = 0;
-        const PtrList &d = dst ? *dst : none;
-        const Finalize off = no_finalize(c);
-        const Finalize &f = fin ? *fin : off;
-        return symv_nv(c) == 2 ? launch_symv_nv<2>(c, s, p, y, partial, sc, d, f) : launch_symv_nv<1>(c, s, p, y, partial, sc, d, f);
+        PtrList d;
+        d.n = 0;
+        if (dst) d = *dst;
+        const Finalize f = fin ? *fin : no_finalize(c);
+        const bool cyc = d.n > 0;
+        const uint64_t n = c->n, ncv = c->ncols_vec();
+        SymvDevPlan &v = s.symv;
+        if (v.tasks == nullptr)
+            LAMCHK(symv_dev_build(c, v, n, ncv, (uint64_t)kBlock * VEC, s.row0, s.nrows, cyc, sizeof(TV), 1, s.stream, "symmetric product"));
+        constexpr unsigned lds_pad = symv_lds_pad<TV, 1>();
+        hipLaunchKernelGGL((cyc ? symv_task_kernel<TA, TV, true> : symv_task_kernel<TA, TV, false>), dim3(v.ntasks), dim3(kBlock), lds_pad,
+                           s.stream, (const TA *)s.A, p, (const SymvTask *)v.tasks, (TV *)v.rowpart, (TV *)v.colpart, c->lda, ncv, n, s.row0, sc);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL((symv_reduce_kernel<TV, kBlock * VEC>), dim3(symv_reduce_grid(n) + (f.active ? 1 : 0)), dim3(kBlock), 0, s.stream,
+                           (const TV *)v.rowpart, (const TV *)v.colpart, (const uint32_t *)v.index, v.ix, p, y,
+                           partial, n, s.row0, s.nrows, d, f, sc);
+        HIPCHK(c, hipGetLastError());
+        c->n_launch += 2;
+        return 0;
     }
 
     // panel: 0 = whole GEMV; 1 = only columns [lo,hi); 2 = everything but [lo,hi), accumulated onto y
@@ -346,13 +310,11 @@ void free_shard(ShardBase &s, bool keep_matrix = false)
     // the row-transfer staging buffer belongs to the context, not to a problem: released only with the matrix
     if (!keep_matrix && s.xfer_stage) { (void)hipFree(s.xfer_stage); s.xfer_stage = nullptr; s.xfer_stage_bytes = 0; }
     void *ptrs[] = {s.A, s.p, s.Ap, s.x, s.r, s.b, s.tmp, s.part_gemv, s.part_vec, s.gather_a, s.gather_b, s.sc,
-                    s.r_full, s.ap_gather, s.symv_rowpart, s.symv_colpart, s.symv_tasks, s.symv_index, s.symv_gather, s.part_aux};
+                    s.r_full, s.ap_gather, s.symv_gather, s.part_aux};
     for (void *q : ptrs) if (q) (void)hipFree(q);
-    s.r_full = s.ap_gather = s.symv_rowpart = s.symv_colpart = s.symv_gather = nullptr;
+    symv_dev_release(s.symv);
+    s.r_full = s.ap_gather = s.symv_gather = nullptr;
     s.symv_gather_bytes = 0;
-    s.symv_tasks = nullptr;
-    s.symv_index = nullptr;
-    s.symv_ntasks = 0;
     if (s.sc_host) (void)hipHostFree(s.sc_host);
     if (s.host_flags) (void)hipHostFree(s.host_flags);
     s.host_flags = nullptr;

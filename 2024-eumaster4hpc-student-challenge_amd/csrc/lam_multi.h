@@ -60,7 +60,7 @@ void multi_release(lam_hip_ctx *c)
     free_dev({m.B, m.X, m.R, m.P, m.AP, m.stage, m.part_gemv, m.part_vec, m.part_rr, m.res, m.sc});
     free_dev({m.ms.XS, m.ms.PS, m.ms.sc});
     free_dev({m.mr.W, m.mr.WOLD, m.mr.sc});
-    free_dev({m.sym_tasks, m.sym_index, m.sym_rowpart, m.sym_colpart});
+    symv_dev_release(m.sym);
     free_dev({m.lz.V, m.lz.U, m.lz.Y, m.lz.part, m.lz.part_uu, m.lz.S, m.lz.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
@@ -256,14 +256,12 @@ int multi_product_blocks(const lam_hip_ctx *c, int K) { return multi_sym_wanted(
 
 void multi_sym_release(MultiState &m)
 {
-    free_dev({m.sym_tasks, m.sym_index, m.sym_rowpart, m.sym_colpart});
-    m.sym_tasks = nullptr; m.sym_index = nullptr; m.sym_rowpart = m.sym_colpart = nullptr;
-    m.sym_ntasks = m.sym_vec = m.sym_cap_K = 0;
-    m.sym_rowpart_elems = 0;
+    symv_dev_release(m.sym);
+    m.sym_vec = m.sym_cap_K = 0;
 }
 
-// Plan (symv_plan as the single product has it: one shard, strips of 256 * VEC columns) at first use for the batch's n; partials for K
-// columns, grow-only.  All of a step or none of it: a failed allocation leaves what there was, and the batch runs on under option 0.
+// Plan (symv_dev_build as the single product has it: one shard, strips of 256 * VEC columns) at first use for the batch's n; partials
+// for K columns, grow-only.  All of a step or none of it: a failed allocation leaves what there was, and the batch runs on under option 0.
 template <typename TA, typename TV>
 int multi_sym_ensure(lam_hip_ctx *c, int K)
 {
@@ -271,39 +269,17 @@ int multi_sym_ensure(lam_hip_ctx *c, int K)
     ShardBase &s = c->sh[0];
     constexpr int VEC = MatVec<TA>::N;
     constexpr uint64_t SS = (uint64_t)kBlock * VEC;
-    if (m.sym_tasks != nullptr && m.sym_vec != VEC) {        // the same n under another storage type: another plan
+    if (m.sym.tasks != nullptr && m.sym_vec != VEC) {        // the same n under another storage type: another plan
         HIPCHK(c, hipStreamSynchronize(s.stream));
         multi_sym_release(m);
     }
-    if (m.sym_tasks == nullptr) {
-        SymvPlan plan;
-        symv_plan(c->n, c->ncols_vec(), SS, 0, c->n, false, &plan);
-        if (plan.tasks.empty()) return fail(c, LAM_HIP_EINVAL, "symmetric batched product: no tasks");
-        if (plan.rowpart_elems >> 32) return fail(c, LAM_HIP_EINVAL, "symmetric batched product: too many row partials for 32-bit offsets");
-        DevBuf t, sb;
-        HIPCHK(c, hipMalloc(&t.p, plan.tasks.size() * sizeof(SymvTask)));
-        HIPCHK(c, hipMalloc(&sb.p, plan.index.size() * sizeof(uint32_t)));
-        HIPCHK(c, hipMemcpy(t.p, plan.tasks.data(), plan.tasks.size() * sizeof(SymvTask), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(sb.p, plan.index.data(), plan.index.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        m.sym_tasks = t.as<SymvTask>(); m.sym_index = sb.as<uint32_t>();
-        t.p = sb.p = nullptr;
-        m.sym_ix = plan.ix;
-        m.sym_ntasks = (int)plan.tasks.size();
-        m.sym_rowpart_elems = plan.rowpart_elems;
+    if (m.sym.tasks == nullptr) {
+        LAMCHK(symv_dev_build(c, m.sym, c->n, c->ncols_vec(), SS, 0, c->n, false, sizeof(TV), K, s.stream, "symmetric batched product"));
         m.sym_vec = VEC;
-        m.sym_cap_K = 0;             // (no partials yet: multi_sym_release has run, or nothing was ever allocated)
+        m.sym_cap_K = K;
     }
     if (K > m.sym_cap_K) {
-        const size_t rbytes = (size_t)m.sym_rowpart_elems * K * sizeof(TV), cbytes = (size_t)m.sym_ntasks * SS * K * sizeof(TV);
-        DevBuf rp, cp;
-        HIPCHK(c, hipMalloc(&rp.p, rbytes));
-        HIPCHK(c, hipMalloc(&cp.p, cbytes));
-        // columns behind the end of a ragged strip are never written by a task: the second pass does not read them either
-        HIPCHK(c, hipMemsetAsync(cp.p, 0, cbytes, s.stream));
-        HIPCHK(c, hipStreamSynchronize(s.stream));           // and no launch on the smaller buffers is in flight
-        free_dev({m.sym_rowpart, m.sym_colpart});
-        m.sym_rowpart = rp.p; m.sym_colpart = cp.p;
-        rp.p = cp.p = nullptr;
+        LAMCHK(symv_dev_partials(c, m.sym, SS, sizeof(TV), K, s.stream));
         m.sym_cap_K = K;
     }
     return 0;
@@ -317,21 +293,16 @@ int multi_sym_launch(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const 
     c->symv_many_effective = false;
     LAMCHK((multi_sym_ensure<TA, TV>(c, K)));
     constexpr int SS = kBlock * MatVec<TA>::N;
-    constexpr unsigned lds_pad = symv_many_lds_pad<TV, K>();
-    hipLaunchKernelGGL((symv_many_task_kernel<TA, TV, K>), dim3(m.sym_ntasks), dim3(kBlock), lds_pad, s.stream,
-                       (const TA *)s.A, P, (const SymvTask *)m.sym_tasks, (TV *)m.sym_rowpart, (TV *)m.sym_colpart, c->lda, c->ncols_vec(),
+    constexpr unsigned lds_pad = symv_lds_pad<TV, K>();
+    hipLaunchKernelGGL((symv_many_task_kernel<TA, TV, K>), dim3(m.sym.ntasks), dim3(kBlock), lds_pad, s.stream,
+                       (const TA *)s.A, P, (const SymvTask *)m.sym.tasks, (TV *)m.sym.rowpart, (TV *)m.sym.colpart, c->lda, c->ncols_vec(),
                        c->n, sc);
     LAUNCHED(c);
     ShiftArg<TV> sa;
     for (int j = 0; j < kSymvManyMaxK; j++) sa.s[j] = shift ? (TV)shift[j] : (TV)0;
-    if (shift)
-        hipLaunchKernelGGL((symv_many_reduce_kernel<TV, SS, K, true>), dim3(multi_sym_grid(c)), dim3(kBlock), 0, s.stream,
-                           (const TV *)m.sym_rowpart, (const TV *)m.sym_colpart, (const uint32_t *)m.sym_index, m.sym_ix, P, Y, partial, c->n,
-                           sa, sc);
-    else
-        hipLaunchKernelGGL((symv_many_reduce_kernel<TV, SS, K, false>), dim3(multi_sym_grid(c)), dim3(kBlock), 0, s.stream,
-                           (const TV *)m.sym_rowpart, (const TV *)m.sym_colpart, (const uint32_t *)m.sym_index, m.sym_ix, P, Y, partial, c->n,
-                           sa, sc);
+    hipLaunchKernelGGL((shift ? symv_many_reduce_kernel<TV, SS, K, true> : symv_many_reduce_kernel<TV, SS, K, false>), dim3(multi_sym_grid(c)),
+                       dim3(kBlock), 0, s.stream, (const TV *)m.sym.rowpart, (const TV *)m.sym.colpart, (const uint32_t *)m.sym.index, m.sym.ix,
+                       P, Y, partial, c->n, sa, sc);
     LAUNCHED(c);
     c->symv_many_effective = true;
     return 0;
@@ -566,7 +537,7 @@ double multi_gemv_bytes(const lam_hip_ctx *c, int K)
     if (c->symv_many_effective)
         return (double)c->esz_a() * ((double)c->n * ((double)c->n + 1.0) / 2.0) + (double)c->esz_v() * 2.0 * (double)K * (double)c->n +
                2.0 * (double)c->esz_v() * (double)K *
-                   ((double)m.sym_rowpart_elems + (double)m.sym_ntasks * (double)kBlock * (16.0 / (double)c->esz_a()));
+                   ((double)m.sym.rowpart_elems + (double)m.sym.ntasks * (double)kBlock * (16.0 / (double)c->esz_a()));
     return (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)K * (double)c->n;
 }
 

@@ -34,11 +34,16 @@ def test_the_product_build_includes_the_same_planner_header():
     its symv_plan / symv_plan_check, and nothing in the header needs HIP."""
     src = os.path.join(ROOT, "2024-eumaster4hpc-student-challenge_amd", "csrc")
     assert '#include "lam_host_plan.h"' in open(os.path.join(src, "lam_kernels.h")).read()
-    assert "symv_plan(n, ncv, SS, s.row0, s.nrows, cyc, &plan)" in open(os.path.join(src, "lam_launch.h")).read()
+    # the one call of the planner: symv_dev_build (lam_ctx.h), which both the single launcher and the batch go through
+    texts = {f: open(os.path.join(src, f)).read() for f in ("lam_ctx.h", "lam_launch.h", "lam_multi.h", "lam_exchange.h", "lam_iterate.h")}
+    assert "symv_plan(n, ncv, SS, row0, nrows, cyc, &plan)" in texts["lam_ctx.h"]
+    assert sum(t.count("symv_plan(") for t in texts.values()) == 1
+    assert "symv_dev_build(c, v, n, ncv, (uint64_t)kBlock * VEC, s.row0, s.nrows, cyc," in texts["lam_launch.h"]
+    assert "symv_dev_build(c, m.sym, c->n, c->ncols_vec(), SS, 0, c->n, false," in texts["lam_multi.h"]
     assert "lam::symv_plan_check(" in open(os.path.join(src, "lam_hip.hip")).read()
     header = open(os.path.join(src, "lam_host_plan.h")).read()
     assert "hip_runtime" not in header and "#include <hip" not in header
-    for other in ("lam_launch.h", "lam_ctx.h", "lam_hip.hip", "lam_kernels.h"):
+    for other in ("lam_launch.h", "lam_ctx.h", "lam_multi.h", "lam_hip.hip", "lam_kernels.h"):
         assert "void symv_plan(" not in open(os.path.join(src, other)).read(), other       # no second copy of the planner
 
 

@@ -1,6 +1,6 @@
 """Option "symmetric_many" without a GPU: the header says what holds, the driver refuses a bad -Y before it touches a device, and the
-compiler's resource report of every instantiation of the two K-wide kernels (cross-compiled for gfx950) shows no scratch and the
-registers that keep three workgroups per CU."""
+compiler's resource report of every instantiation of the two K-wide kernels, and of the single symmetric product's kernels, whose
+second pass is the same body (cross-compiled for gfx950), shows no scratch and the registers that keep three workgroups per CU."""
 import os
 import re
 import shutil
@@ -33,6 +33,9 @@ def test_driver_refuses_a_bad_value_before_touching_a_gpu(lam):
 
 
 INSTANTIATIONS = [(t, k) for t in ("double", "float") for k in (1, 2, 4)]
+# the single product's entry points the library launches: (storage, vectors, columns of a strip), CYC false and true each
+SINGLE = [("double", "double", 512), ("float", "float", 1024), ("__hip_bfloat16", "float", 2048)]
+ITANIUM = {"double": "d", "float": "f", "__hip_bfloat16": "14__hip_bfloat16"}
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs the ROCm compiler")
@@ -48,6 +51,12 @@ def test_resource_report_has_no_scratch_and_keeps_three_workgroups_per_cu(tmp_pa
         for shift in ("true", "false"):
             lines.append(f"template __global__ void lam::symv_many_reduce_kernel<{t}, {ss}, {k}, {shift}>(const {t} *, const {t} *, "
                          f"const uint32_t *, SymvIndex, const {t} *, {t} *, double *, uint64_t, ShiftArg<{t}>, const MultiScalars *);")
+    for ta, t, ss in SINGLE:
+        for cyc in ("false", "true"):
+            lines.append(f"template __global__ void lam::symv_task_kernel<{ta}, {t}, {cyc}>(const {ta} *, const {t} *, const SymvTask *, {t} *, "
+                         f"{t} *, uint64_t, uint64_t, uint64_t, uint64_t, const CgScalars *);")
+        lines.append(f"template __global__ void lam::symv_reduce_kernel<{t}, {ss}>(const {t} *, const {t} *, const uint32_t *, SymvIndex, "
+                     f"const {t} *, {t} *, double *, uint64_t, uint64_t, uint64_t, PtrList, Finalize, const CgScalars *);")
     src = tmp_path / "symv_many_resources.hip"
     src.write_text("\n".join(lines) + "\n")
     r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"),
@@ -64,7 +73,7 @@ def test_resource_report_has_no_scratch_and_keeps_three_workgroups_per_cu(tmp_pa
     filt = shutil.which("c++filt")
     names = list(seen)
     dem = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True).stdout.splitlines() if filt else names
-    tasks = reduces = 0
+    tasks = reduces = single_tasks = single_reduces = 0
     for name, d in zip(names, dem):
         res = seen[name]
         print(f"{d[:110]:110s} {res}")
@@ -75,7 +84,17 @@ def test_resource_report_has_no_scratch_and_keeps_three_workgroups_per_cu(tmp_pa
         elif "symv_many_reduce_kernel" in name:
             reduces += 1
             assert res["vgpr"] + res["agpr"] <= 128 and res["waves"] >= 4, (d, res)
+        elif "symv_task_kernel" in name:
+            single_tasks += 1
+            assert res["vgpr"] + res["agpr"] <= 168, (d, res)
+        elif "symv_reduce_kernel" in name:
+            single_reduces += 1
+            assert res["vgpr"] + res["agpr"] <= 128 and res["waves"] >= 4, (d, res)
     assert tasks == len(INSTANTIATIONS) and reduces == 2 * len(INSTANTIATIONS), sorted(dem)
+    assert single_tasks == 2 * len(SINGLE) and single_reduces == len(SINGLE), sorted(dem)
+    for ta, t, ss in SINGLE:                # K = 1: 4 waves x 256 rows x one element of the vector type
+        mangled = [n for n in names if "symv_task_kernel" in n and f"I{ITANIUM[ta]}{ITANIUM[t]}Lb" in n]
+        assert len(mangled) == 2 and all(seen[m]["lds"] == 4 * 256 * (8 if t == "double" else 4) for m in mangled), (ta, t, mangled)
     for t, k in INSTANTIATIONS:
         mangled = [n for n in names if "symv_many_task_kernel" in n and f"I{'d' if t == 'double' else 'f'}{'d' if t == 'double' else 'f'}Li{k}E" in n]
         assert len(mangled) == 1 and seen[mangled[0]]["lds"] == 4 * 256 * k * (8 if t == "double" else 4), (t, k, mangled)

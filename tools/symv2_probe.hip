@@ -1,3 +1,5 @@
+// The two-vectors-per-lane rows (NV = 2) of profiles/r04_symv2_probe.txt were measured on the kernels as of commit 7e8acf6 and before: the
+// library's kernels no longer have that shape, and this probe's schedules for it are cut (a spec with NV = 2 is refused).
 // symv2_probe -- research probe, NOT part of the product: drives the PRODUCT's symmetric-product kernels (csrc/lam_kernels.h, included below)
 // with its own task schedules, several plans timed INTERLEAVED in one process (the device's state and the placement of a plan's buffers move
 // this kernel by several percent; only interleaved numbers compare), against a plain full-matrix product on the same data.
@@ -6,7 +8,7 @@
 // current shape is on file in profiles/r04_symv2_probe.txt.
 //
 // usage: symv2_probe.out N f64|f32 rounds SPEC ...        SPEC = [KiB*100+]NV:h1@f1,h2@f2,...,hlast
-//        NV = 16-byte vectors per lane and row (1 | 2), KiB = idle dynamic LDS per workgroup of the first pass (caps the workgroups per CU),
+//        NV = 16-byte vectors per lane and row (1; 2 is no longer compiled), KiB = idle dynamic LDS per workgroup of the first pass (caps the workgroups per CU),
 //        schedule: tasks of h1 rows up to row f1 * N, h2 up to f2 * N, ..., hlast for the rest (heights: multiples of 8, at most 2048)
 // environment: SYMV2_SHARD=q/P  one row shard of a P-way split (cyclic half windows)      SYMV2_READONLY=1  also time the tasks' loads alone
 //              SYMV2_REVERSE=1  time the plans in reverse order      SYMV2_PAD_MB=n  an idle allocation between the matrix and the plans' buffers
@@ -154,13 +156,10 @@ bool pass1(const Plan<T> &pl, const T *A, const T *p, uint64_t n, uint64_t lda, 
 {
     if (g_shard_P > 0) {
         const uint64_t R0 = g_shard_q * (n / g_shard_P);
-        if (pl.NV == 1) hipLaunchKernelGGL((lam::symv_task_kernel<T, T, 1, true>), dim3(pl.ntasks), dim3(kBlock), 0, g_stream, A + R0 * lda, p, pl.dt, pl.rowpart, pl.colpart, lda, ncols_vec, n, R0, (const lam::CgScalars *)nullptr);
-        else hipLaunchKernelGGL((lam::symv_task_kernel<T, T, 2, true>), dim3(pl.ntasks), dim3(kBlock), 0, g_stream, A + R0 * lda, p, pl.dt, pl.rowpart, pl.colpart, lda, ncols_vec, n, R0, (const lam::CgScalars *)nullptr);
+        hipLaunchKernelGGL((lam::symv_task_kernel<T, T, true>), dim3(pl.ntasks), dim3(kBlock), 0, g_stream, A + R0 * lda, p, pl.dt, pl.rowpart, pl.colpart, lda, ncols_vec, n, R0, (const lam::CgScalars *)nullptr);
         return true;
     }
-    if (pl.NV == 1) hipLaunchKernelGGL((lam::symv_task_kernel<T, T, 1, false>), dim3(pl.ntasks), dim3(kBlock), pl.lds_extra, g_stream, A, p, pl.dt, pl.rowpart, pl.colpart, lda, ncols_vec, n, (uint64_t)0, (const lam::CgScalars *)nullptr);
-    else if (pl.NV == 2) hipLaunchKernelGGL((lam::symv_task_kernel<T, T, 2, false>), dim3(pl.ntasks), dim3(kBlock), pl.lds_extra, g_stream, A, p, pl.dt, pl.rowpart, pl.colpart, lda, ncols_vec, n, (uint64_t)0, (const lam::CgScalars *)nullptr);
-    else return false;
+    hipLaunchKernelGGL((lam::symv_task_kernel<T, T, false>), dim3(pl.ntasks), dim3(kBlock), pl.lds_extra, g_stream, A, p, pl.dt, pl.rowpart, pl.colpart, lda, ncols_vec, n, (uint64_t)0, (const lam::CgScalars *)nullptr);
     return true;
 }
 template <typename T>
@@ -173,13 +172,10 @@ bool pass2(const Plan<T> &pl, const T *p, T *y, double *partial, uint64_t n, uin
     nofin.active = 0; nofin.mail = 0; nofin.seq = 0; nofin.dst.n = 0; nofin.slot = 0; nofin.host_err = nullptr;
     if (g_shard_P > 0) {
         const uint64_t nloc = n / g_shard_P, R0 = g_shard_q * nloc;
-        if (pl.NV == 1) hipLaunchKernelGGL((lam::symv_reduce_kernel<T, 1 * lam::kBlock * Vec<T>::N>), dim3(grid), dim3(kBlock), 0, g_stream, pl.rowpart, pl.colpart, pl.dsb, pl.ix, p, y, partial, n, R0, nloc, none, nofin, (const lam::CgScalars *)nullptr);
-        else hipLaunchKernelGGL((lam::symv_reduce_kernel<T, 2 * lam::kBlock * Vec<T>::N>), dim3(grid), dim3(kBlock), 0, g_stream, pl.rowpart, pl.colpart, pl.dsb, pl.ix, p, y, partial, n, R0, nloc, none, nofin, (const lam::CgScalars *)nullptr);
+        hipLaunchKernelGGL((lam::symv_reduce_kernel<T, lam::kBlock * Vec<T>::N>), dim3(grid), dim3(kBlock), 0, g_stream, pl.rowpart, pl.colpart, pl.dsb, pl.ix, p, y, partial, n, R0, nloc, none, nofin, (const lam::CgScalars *)nullptr);
         return true;
     }
-    if (pl.NV == 1) hipLaunchKernelGGL((lam::symv_reduce_kernel<T, 1 * lam::kBlock * Vec<T>::N>), dim3(grid), dim3(kBlock), 0, g_stream, pl.rowpart, pl.colpart, pl.dsb, pl.ix, p, y, partial, n, (uint64_t)0, n, none, nofin, (const lam::CgScalars *)nullptr);
-    else if (pl.NV == 2) hipLaunchKernelGGL((lam::symv_reduce_kernel<T, 2 * lam::kBlock * Vec<T>::N>), dim3(grid), dim3(kBlock), 0, g_stream, pl.rowpart, pl.colpart, pl.dsb, pl.ix, p, y, partial, n, (uint64_t)0, n, none, nofin, (const lam::CgScalars *)nullptr);
-    else return false;
+    hipLaunchKernelGGL((lam::symv_reduce_kernel<T, lam::kBlock * Vec<T>::N>), dim3(grid), dim3(kBlock), 0, g_stream, pl.rowpart, pl.colpart, pl.dsb, pl.ix, p, y, partial, n, (uint64_t)0, n, none, nofin, (const lam::CgScalars *)nullptr);
     return true;
 }
 
@@ -215,6 +211,7 @@ int run(uint64_t n, const std::vector<std::string> &specs, int rounds)
         if (sscanf(spec.c_str(), "%d:%255s", &pl.NV, sched) != 2) { printf("bad spec %s\n", spec.c_str()); return 1; }
         pl.lds_extra = (unsigned)(pl.NV / 100) * 1024u;
         pl.NV %= 100;
+        if (pl.NV != 1) { printf("shape of %s not compiled in: the library's kernels have one vector per lane and row\n", spec.c_str()); return 1; }
         for (char *tok = strtok(sched, ","); tok; tok = strtok(nullptr, ",")) {
             int hgt = 0; double f = 2.0;
             if (sscanf(tok, "%d@%lf", &hgt, &f) < 1 || hgt % 8 || hgt > kRowsMax || hgt <= 0) { printf("bad schedule %s\n", tok); return 1; }
@@ -342,10 +339,8 @@ int main(int argc, char **argv)
     const uint64_t n = strtoull(argv[1], nullptr, 10);
     const bool f32 = !strcmp(argv[2], "f32");
     if (getenv("SYMV2_STREAM")) CHK(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-    (void)hipFuncSetAttribute((const void *)lam::symv_task_kernel<double, double, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute((const void *)lam::symv_task_kernel<double, double, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute((const void *)lam::symv_task_kernel<float, float, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute((const void *)lam::symv_task_kernel<float, float, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)lam::symv_task_kernel<double, double, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)lam::symv_task_kernel<float, float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pattern_read_kernel<double, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pattern_read_kernel<double, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pattern_read_kernel<float, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
