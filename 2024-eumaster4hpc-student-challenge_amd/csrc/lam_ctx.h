@@ -230,34 +230,20 @@ struct lam_hip_ctx {
     int64_t opt_gemv_timing = 8;   // HIP-event pair around the GEMV of every T-th iteration (t_gemv of the stats); 0 = never.
                                    // Every record is a marker packet between the kernels: timing every iteration costs 8 us
                                    // per iteration (profiles/r03_event_cost.txt)
-    // One process, several shards: how the host orders the shards' streams (profiles/r03_host_enqueue_cost.txt).  Every
+    // One process, several shards: the host orders the shards' streams with events (profiles/r03_host_enqueue_cost.txt).  Every
     // cross-stream event operation costs the host 3-5 us, so the event-based forms all stay above 0.2 ms per iteration
     // at P = 8; the form that does not (no events at all) is the in-kernel flag exchange, option "exchange" = 2.
-    int64_t opt_host_threads = 0;  // 1 = every shard is enqueued by a host thread of its own (the reference's shape)
-    int64_t opt_hub = 0;           // 1 = the shards' streams meet at ONE join event per exchange (P waits on a hub stream +
-                                   // P waits on its event: 3(3P+1) calls per iteration) instead of every stream waiting
-                                   // for every other one (3P^2 calls); fewer host calls, one more event hop on the device
-    hipStream_t hub_stream = nullptr;          // on shard 0's device
-    hipEvent_t ev_join[3] = {};                // p.Ap partials posted / r.r partials posted / p slices stored
+    hipEvent_t ev_join = nullptr;  // gather-Ap, option exchange_join: recorded on shard 0's stream once every shard has posted
     int64_t opt_assume_cus = 0;    // testing: pretend the device has this many CUs when checking that a launch whose
                                    // workgroups wait for each other is fully resident (0 = ask the device)
     bool fuse_active = false;      // the current CG state uses update_fused_kernel (decided in cg_init: option + residency)
-    // whole-iteration persistent launch (lam_kernels.h, cg_persist_kernel): EXPERIMENT, option "persistent", off by default
-    int64_t opt_persistent = 0;
-    int64_t opt_persist_chunk = 32;             // iterations per launch
-    bool persist_active = false;                // the current CG state runs on it (decided in cg_init)
-    int persist_W = 0;                          // worker workgroups (+ 1 reducer)
-    BcastLine *persist_bc = nullptr;            // [kVecBlocksMax + persist lines] broadcast lines (device memory)
-    unsigned long long *persist_ticks = nullptr;        // device: [0] GEMV-phase ticks (100 MHz), [1] phases
-    unsigned long long *persist_ticks_host = nullptr;   // pinned mirror
     // runtime calls issued by the iteration loop (diagnostics: host cost of an iteration, tools/host_enqueue_cost.py)
-    std::atomic<uint64_t> n_launch{0}, n_record{0}, n_wait{0}, n_setdev{0};
+    uint64_t n_launch = 0, n_record = 0, n_wait = 0, n_setdev = 0;
     uint64_t enqueue_ns = 0;       // host time spent issuing iterations (the waits for the device's progress excluded)
     uint64_t host_cpu_ns = 0;      // CPU time (CLOCK_THREAD_CPUTIME_ID) the calling thread spent inside lam_hip_cg_iterate
     double iter_est_s = 0.0;       // observed seconds per iteration (await_progress sleeps a fraction of it between polls)
     double prog_t = 0.0;           // when / at which iteration the last awaited progress was seen
     int prog_iter = 0;
-    std::mutex err_mu;             // `err` may be written by the per-shard enqueue threads
     // direct exchange (option exchange = 2): peer-mapped p replicas and mailboxes (lam_kernels.h, Mail)
     Mail *peer_mail[kMaxShards] = {};           // every shard's mailbox as seen from this process (own included)
     void *peer_p[kMaxShards] = {};              // every shard's p replica as seen from this process (own included)
@@ -330,7 +316,7 @@ int fail(lam_hip_ctx *c, int code, const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    if (c) { std::lock_guard<std::mutex> lk(c->err_mu); c->err = buf; }
+    if (c) c->err = buf;
     else g_create_error = buf;
     return code;
 }

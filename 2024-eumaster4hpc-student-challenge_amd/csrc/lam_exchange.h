@@ -159,13 +159,11 @@ int create_common(lam_hip_ctx *c)
                 for (auto &ev : s.ev_x[i])
                     if (hipEventCreate(&ev) != hipSuccess) return fail(nullptr, LAM_HIP_EHIP, "hipEventCreate failed");
     }
-    // hub of the one-process exchange (see hub_join): a stream on shard 0's device and one join event per exchange
+    // the join event of the one-process gather-Ap exchange (option exchange_join), on shard 0's device
     if (!c->rank_mode && c->sh.size() > 1) {
-        if (hipSetDevice(c->sh[0].dev) != hipSuccess || hipStreamCreateWithFlags(&c->hub_stream, hipStreamNonBlocking) != hipSuccess)
-            return fail(nullptr, LAM_HIP_EHIP, "hipStreamCreate (hub) failed");
-        for (auto &ev : c->ev_join)
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess)
-                return fail(nullptr, LAM_HIP_EHIP, "hipEventCreate failed");
+        if (hipSetDevice(c->sh[0].dev) != hipSuccess ||
+            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess)
+            return fail(nullptr, LAM_HIP_EHIP, "hipEventCreate failed");
     }
     // the error word of the bounded in-kernel waits (reducer workgroups, fused update, direct exchange)
     if (hipSetDevice(c->sh[0].dev) != hipSuccess || hipHostMalloc((void **)&c->direct_err, 64, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
@@ -289,10 +287,9 @@ Finalize make_finalize(lam_hip_ctx *c, ShardBase &s, bool second)
 //   rank mode          : in-place ncclAllGather of the 8-byte partials (slot = rank)
 // `finalized` = the producer kernel already reduced its partials (Finalize); otherwise a 1-block
 // finalize_sum_kernel does it here (cg_init, and option "finalize" = 0).
-// Two halves per shard, so that every shard can be driven by a host thread of its own: reduce_post is what the
-// PRODUCING shard puts on its stream behind the producer kernel, reduce_wait makes a CONSUMING shard's stream wait
-// for its peers' posts -- which must all have been issued by then (single thread: post for all shards, then wait
-// for all; threads: a host barrier in between).  The shard's device is current in both.
+// Two halves per shard: reduce_post is what the PRODUCING shard puts on its stream behind the producer kernel,
+// reduce_wait makes a CONSUMING shard's stream wait for its peers' posts -- which must all have been issued by then
+// (post for all shards, then wait for all).  The shard's device is current in both.
 int reduce_post(lam_hip_ctx *c, ShardBase &s, bool second, bool use_gemv_part, bool check_stop, bool finalized)
 {
     if (!c->rank_mode && c->total_shards == 1) return 0;
@@ -316,37 +313,15 @@ int reduce_post(lam_hip_ctx *c, ShardBase &s, bool second, bool use_gemv_part, b
     return 0;
 }
 
-// Is the all-to-all ordering between the shards' streams done through the hub?
-#ifdef LAM_TUNING_VARIANTS
-bool hub_active(const lam_hip_ctx *c) { return !c->rank_mode && c->total_shards > 2 && c->opt_hub != 0 && c->hub_stream != nullptr; }
-#else
-constexpr bool hub_active(const lam_hip_ctx *) { return false; }     // tuning build only (measured slower in wall time)
-#endif
-
-// One process, several shards: after every shard has posted exchange `which` (0 = p.Ap partials, 1 = r.r partials,
-// 2 = p slices), the hub stream waits for the P posts and records ONE join event; every shard then waits for that
-// event -- 2P + 1 runtime calls where the all-to-all form needs P(P-1) (P = 8: 17 instead of 56).  The join adds
-// one event hop on the device; every stream still depends on every post (the hub's wait list is all of them), and the
-// events carry the same system-scope release / acquire as before.
-int hub_join(lam_hip_ctx *c, int which)
-{
-    if (!hub_active(c)) return 0;
-    LAMCHK(set_dev(c, c->sh[0]));
-    for (auto &t : c->sh) WAITEV(c, c->hub_stream, which == 0 ? t.ev_a : (which == 1 ? t.ev_b : t.ev_p));
-    RECORD(c, c->ev_join[which], c->hub_stream);
-    return 0;
-}
-
 int reduce_wait(lam_hip_ctx *c, ShardBase &s, bool second)
 {
     if (c->rank_mode || c->total_shards == 1) return 0;
-    if (hub_active(c)) { WAITEV(c, s.stream, c->ev_join[second ? 1 : 0]); return xt_end(c, s, s.stream); }
     for (auto &t : c->sh)
         if (&t != &s) WAITEV(c, s.stream, second ? t.ev_b : t.ev_a);
     return xt_end(c, s, s.stream);
 }
 
-// both halves for all shards from one thread (cg_init)
+// both halves for all shards (cg_init)
 int reduce_step(lam_hip_ctx *c, bool second, bool use_gemv_part, bool check_stop, bool finalized)
 {
     if (!c->rank_mode && c->total_shards == 1) return 0;
@@ -354,7 +329,6 @@ int reduce_step(lam_hip_ctx *c, bool second, bool use_gemv_part, bool check_stop
         LAMCHK(set_dev(c, s));
         LAMCHK(reduce_post(c, s, second, use_gemv_part, check_stop, finalized));
     }
-    LAMCHK(hub_join(c, second ? 1 : 0));
     for (auto &s : c->sh) {
         LAMCHK(set_dev(c, s));
         LAMCHK(reduce_wait(c, s, second));
@@ -429,13 +403,12 @@ int gather_post(lam_hip_ctx *c, ShardBase &s)
 int gather_wait(lam_hip_ctx *c, ShardBase &s)
 {
     if (c->rank_mode || c->total_shards == 1) return 0;
-    if (hub_active(c)) { WAITEV(c, s.stream, c->ev_join[2]); return xt_end(c, s, s.stream); }
     for (auto &t : c->sh)
         if (&t != &s) WAITEV(c, s.stream, t.ev_p);
     return xt_end(c, s, s.stream);
 }
 
-// make every replica of p complete after the slices were stored (all shards, one thread: cg_init)
+// make every replica of p complete after the slices were stored (all shards: cg_init)
 int gather_p_step(lam_hip_ctx *c)
 {
     if (!c->rank_mode && c->total_shards == 1) return 0;
@@ -444,7 +417,6 @@ int gather_p_step(lam_hip_ctx *c)
         LAMCHK(set_dev(c, s));
         LAMCHK(gather_post(c, s));
     }
-    LAMCHK(hub_join(c, 2));
     for (auto &s : c->sh) {
         LAMCHK(set_dev(c, s));
         LAMCHK(gather_wait(c, s));
@@ -641,8 +613,7 @@ bool timed_iteration(const lam_hip_ctx *c, const ShardBase &s, int k)
 // ---- the product step of an iteration, written once (every exchange's enqueue code launches its product through these) --------
 // The timing bracket: `launch` runs between the event pair of ring slot `slot` when iteration k is timed, and the slot's bookkeeping
 // (timed_slot, split_slot: what harvest_shard reads) is kept here.  A product in two panels brackets each one, the second with
-// `second` (ev_g2 / ev_g3), so that t_gemv is kernel time and not what happens between the panels.  Touches the shard only: each of
-// the tuning build's enqueue threads calls it for its own shard.
+// `second` (ev_g2 / ev_g3), so that t_gemv is kernel time and not what happens between the panels.
 template <typename F>
 int timed_product(lam_hip_ctx *c, ShardBase &s, int k, int slot, bool second, F &&launch)
 {
@@ -963,12 +934,12 @@ int enqueue_iteration_exchange1_local(lam_hip_ctx *c, int k, double rel_error, i
             for (auto &t : c->sh)
                 if (&t != &s0) WAITEV(c, s0.stream, t.ev_a);
             LAMCHK(xt_end(c, s0, s0.stream));
-            RECORD(c, c->ev_join[0], s0.stream);
+            RECORD(c, c->ev_join, s0.stream);
         }
         for (auto &s : c->sh) {
             LAMCHK(set_dev(c, s));
             if (c->opt_join) {
-                if (&s != &c->sh[0]) WAITEV(c, s.stream, c->ev_join[0]);
+                if (&s != &c->sh[0]) WAITEV(c, s.stream, c->ev_join);
             } else {
                 for (auto &t : c->sh)
                     if (&t != &s) WAITEV(c, s.stream, t.ev_a);

@@ -32,7 +32,6 @@
 #include <new>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -197,12 +196,7 @@ void lam_hip_destroy(lam_hip_ctx *c)
     }
     if (c->direct_err) (void)hipHostFree(c->direct_err);
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (!c->sh.empty() && hipSetDevice(c->sh[0].dev) == hipSuccess) {
-        if (c->persist_bc) (void)hipFree(c->persist_bc);
-        if (c->persist_ticks) (void)hipFree(c->persist_ticks);
-        if (c->persist_ticks_host) (void)hipHostFree(c->persist_ticks_host);
-    }
-    release_hub(c);
+    release_join(c);
     for (auto &s : c->sh) {
         free_shard(s);
         release_handles(s);
@@ -606,34 +600,7 @@ int lam_hip_cg_iterate(lam_hip_ctx *c, int iters, double rel_error, lam_hip_stat
         for (int i = 0; i < kLag; i++) { sh_.timed_slot[i] = false; sh_.nx[i] = 0; }
     if (stopped) {
         // nothing to enqueue
-    }
-#ifdef LAM_TUNING_VARIANTS
-    else if (c->persist_active) {
-        // whole-iteration launches of `chunk` iterations; at most two of them are in the queue (the host waits for the
-        // last iteration of the launch before the previous one to report).  After a stop the queued launch returns at once.
-        const int chunk = (int)std::max<int64_t>(1, c->opt_persist_chunk);
-        int prev_last = 0, prev_prev_last = 0;
-        for (int done = 0; done < iters; ) {
-            const int cnt = std::min(chunk, iters - done);
-            if (prev_prev_last != 0) {
-                Progress pr;
-                LAMCHK(await_progress(c, s0, prev_prev_last, &pr));
-                if (pr.stop_at != 0 || *(volatile int *)c->direct_err != 0) break;
-            }
-            const double te = now_s();
-            LAMCHK(enqueue_persist_chunk(c, k_first + done, cnt, rel_error));
-            c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
-            done += cnt;
-            prev_prev_last = prev_last;
-            prev_last = k_first + done - 1;
-            enq += cnt;
-        }
-    } else if (!c->rank_mode && c->total_shards > 1 && c->opt_host_threads != 0 && !c->cg_direct && !c->cg_exchange1) {
-        LAMCHK(iterate_threaded(c, iters, k_first, rel_error, &enq, &times));
-        c->gather_pending = false;
-    }
-#endif
-    else {
+    } else {
         for (int i = 0; i < iters; i++) {
             const int k = k_first + i;
             const int slot = i % kLag;
@@ -708,17 +675,6 @@ int lam_hip_cg_iterate(lam_hip_ctx *c, int iters, double rel_error, lam_hip_stat
         c->t_gemv_max = tmax;
         st->t_gemv = tmax;
         st->t_exchange = times.samples[0] > 0 ? times.xch_ms * 1e-3 / times.samples[0] : 0.0;
-#ifdef LAM_TUNING_VARIANTS
-        if (c->persist_active && c->persist_ticks != nullptr) {
-            // the persistent launch times its GEMV phases itself (constant-rate 100 MHz counter, reducer workgroup):
-            // from the previous hand-over to the moment the last partial of p.Ap has been summed
-            unsigned long long before[2] = {c->persist_ticks_host[0], c->persist_ticks_host[1]};
-            HIPCHK(c, hipMemcpyAsync(c->persist_ticks_host, c->persist_ticks, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s0.stream));
-            HIPCHK(c, hipStreamSynchronize(s0.stream));
-            const unsigned long long dt = c->persist_ticks_host[0] - before[0], dn = c->persist_ticks_host[1] - before[1];
-            st->t_gemv = dn > 0 ? (double)dt * 1e-8 / (double)dn : 0.0;
-        }
-#endif
         st->t_comm_init = c->t_comm_init;
         st->gemv_bytes = (double)c->esz_a() * (double)s0.nrows * (double)c->n + (double)c->esz_v() * (double)(c->n + s0.nrows);
     }
@@ -1089,16 +1045,17 @@ static constexpr bool kTuningBuild = true;
 #else
 static constexpr bool kTuningBuild = false;
 #endif
-static const char *const kTuningOnly = "%s is an experiment that did not win: it exists in the tuning build only (`make tuning`, load "
-                                       "liblam_hip_tuning.so through LAM_HIP_LIB), not in the product library";
 
 int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
 {
     if (!c || !name) return LAM_HIP_EINVAL;
     if (!strcmp(name, "gemv_variant")) {
-        if (value >= 0 && !Impl<double, double>::variant_available((int)value))
-            return fail(c, LAM_HIP_EINVAL, "gemv_variant %lld is a tuning shape: not in the product library (build `make tuning` and "
-                                           "load liblam_hip_tuning.so, see tools/gemv_probe.py)", (long long)value);
+        // negative: the dtype's default; else a shape this build holds for this dtype (the int64 must survive the narrowing)
+        const bool known = value < 0 || (value == (int64_t)(int)value &&
+                                         dispatch(c, [&](auto impl) -> int { return decltype(impl)::variant_available((int)value); }) == 1);
+        if (!known)
+            return fail(c, LAM_HIP_EINVAL, "gemv_variant %lld: the shapes are 0, 10, 13 and 17 (-1: the dtype's default); the tuning build (`make tuning`, "
+                                           "load liblam_hip_tuning.so through LAM_HIP_LIB) adds 20 and 21 for LAM_HIP_BF16", (long long)value);
         c->opt_gemv_variant = value;
     }
     else if (!strcmp(name, "nt_loads")) c->opt_nt = value;
@@ -1108,17 +1065,14 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
     else if (!strcmp(name, "exchange")) { c->opt_exchange = value; c->cg_ready = false; }
     else if (!strcmp(name, "exchange_join")) c->opt_join = value;
     else if (!strcmp(name, "finalize")) {
-        if (value == 0 && !kTuningBuild) return fail(c, LAM_HIP_EINVAL, kTuningOnly, "finalize = 0 (separate reduction launches, the round-1 chain)");
+        if (value == 0 && !kTuningBuild)
+            return fail(c, LAM_HIP_EINVAL, "finalize = 0 (separate reduction launches, the round-1 chain) exists in the tuning build only (`make tuning`, "
+                                           "load liblam_hip_tuning.so through LAM_HIP_LIB), not in the product library");
         c->opt_finalize = value; c->cg_ready = false;
     }
     else if (!strcmp(name, "upload_staging")) c->opt_upload_staging = value;
     else if (!strcmp(name, "reuse_matrix")) c->opt_reuse_matrix = value;
     else if (!strcmp(name, "fuse_update")) { c->opt_fuse = value; c->cg_ready = false; }
-    else if (!strcmp(name, "persistent") || !strcmp(name, "persist_chunk")) {
-        if (!kTuningBuild && !(value == 0 && !strcmp(name, "persistent"))) return fail(c, LAM_HIP_EINVAL, kTuningOnly, "the whole-iteration persistent launch");
-        if (!strcmp(name, "persistent")) { c->opt_persistent = value; c->cg_ready = false; }
-        else c->opt_persist_chunk = value;
-    }
     else if (!strcmp(name, "symmetric")) {
         // the caller vouches for A = A^T from here on: the environment's check (and a refusal it made) no longer applies to this context
         c->opt_symmetric = value;
@@ -1135,11 +1089,6 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
     }
     else if (!strcmp(name, "gemv_timing")) c->opt_gemv_timing = value < 0 ? 0 : value;
     else if (!strcmp(name, "verify_direct")) c->opt_verify_direct = value;
-    else if (!strcmp(name, "host_threads") || !strcmp(name, "exchange_hub")) {
-        if (value != 0 && !kTuningBuild) return fail(c, LAM_HIP_EINVAL, kTuningOnly, name);
-        if (!strcmp(name, "host_threads")) c->opt_host_threads = value;
-        else c->opt_hub = value;
-    }
     else if (!strcmp(name, "assume_cus")) { c->opt_assume_cus = value; c->cg_ready = false; }
     else if (!strcmp(name, "panel_lo")) c->opt_panel_lo = value;
     else if (!strcmp(name, "panel_hi")) c->opt_panel_hi = value;
@@ -1174,25 +1123,19 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "ranks_on_device")) *value = c->ranks_on_device;
     else if (!strcmp(name, "gemv_ns_min_shard")) *value = (int64_t)(c->t_gemv_min * 1e9);
     else if (!strcmp(name, "gemv_ns_max_shard")) *value = (int64_t)(c->t_gemv_max * 1e9);
-    else if (!strcmp(name, "tuning_variants")) *value = Impl<double, double>::variant_available(1) ? 1 : 0;
+    else if (!strcmp(name, "tuning_variants")) *value = kTuningBuild ? 1 : 0;
     else if (!strcmp(name, "fuse_effective")) *value = c->fuse_active ? 1 : 0;
-    else if (!strcmp(name, "persistent")) *value = c->opt_persistent;
-    else if (!strcmp(name, "persistent_effective")) *value = c->persist_active ? 1 : 0;
-    else if (!strcmp(name, "persistent_workers")) *value = c->persist_active ? c->persist_W : 0;
-    else if (!strcmp(name, "persist_chunk")) *value = c->opt_persist_chunk;
     else if (!strcmp(name, "gemv_timing")) *value = c->opt_gemv_timing;
     else if (!strcmp(name, "verify_direct")) *value = c->opt_verify_direct;
     else if (!strcmp(name, "direct_fallbacks")) *value = c->direct_fallbacks;
-    else if (!strcmp(name, "host_threads")) *value = c->opt_host_threads;
-    else if (!strcmp(name, "exchange_hub")) *value = c->opt_hub;
     else if (!strcmp(name, "assume_cus")) *value = c->opt_assume_cus;
     else if (!strcmp(name, "host_enqueue_ns")) *value = (int64_t)c->enqueue_ns;
     else if (!strcmp(name, "host_cpu_ns")) *value = (int64_t)c->host_cpu_ns;
     else if (!strcmp(name, "row_pitch")) *value = (int64_t)c->lda;
-    else if (!strcmp(name, "hip_calls_launch")) *value = (int64_t)c->n_launch.load();
-    else if (!strcmp(name, "hip_calls_record")) *value = (int64_t)c->n_record.load();
-    else if (!strcmp(name, "hip_calls_wait")) *value = (int64_t)c->n_wait.load();
-    else if (!strcmp(name, "hip_calls_setdevice")) *value = (int64_t)c->n_setdev.load();
+    else if (!strcmp(name, "hip_calls_launch")) *value = (int64_t)c->n_launch;
+    else if (!strcmp(name, "hip_calls_record")) *value = (int64_t)c->n_record;
+    else if (!strcmp(name, "hip_calls_wait")) *value = (int64_t)c->n_wait;
+    else if (!strcmp(name, "hip_calls_setdevice")) *value = (int64_t)c->n_setdev;
     else if (!strcmp(name, "symmetric")) *value = c->opt_symmetric;
     else if (!strcmp(name, "symmetric_many")) *value = c->opt_symmetric_many;
     else if (!strcmp(name, "symmetric_many_effective")) *value = c->symv_many_effective ? 1 : 0;

@@ -1,95 +1,8 @@
-// lam_iterate.h -- one CG iteration per shard (phases, enqueue), cg_init, the host's view of the progress word, the lag rule; tuning build: persistent launch, enqueue threads.
+// lam_iterate.h -- one CG iteration per shard (phases, enqueue), cg_init, the host's view of the progress word, the lag rule.
 // Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 #pragma once
 
 namespace {
-
-#ifdef LAM_TUNING_VARIANTS
-// ---- TUNING BUILD ONLY: the whole-iteration persistent launch (experiment; measured 0.7-2 % slower than the two-launch chain)
-constexpr int kPersistLinesMax = 2048;      // >= the most worker workgroups a device can hold (8 x 256 CUs)
-
-// Can the current CG state run on the whole-iteration persistent launch, and with how many workers?  One shard, fp64 /
-// fp32, the fast GEMV path, not the symmetric product; the grid (W workers + the reducer) must be RESIDENT at once --
-// its workgroups wait for each other for the whole launch -- so W comes from the occupancy query (capped at 8 workgroups
-// of 256 threads per CU), rounded down to a multiple of the number of p tiles (every worker's pairs then share one
-// rotated tile order, which is what lets a group of pairs share a staged tile).
-int decide_persistent(lam_hip_ctx *c)
-{
-    c->persist_active = false;
-    if (c->persist_ticks_host) c->persist_ticks_host[0] = c->persist_ticks_host[1] = 0;
-    if (!c->opt_persistent || c->rank_mode || c->total_shards != 1 || c->dtype == LAM_HIP_BF16 || c->symv_active() || !c->opt_finalize) return 0;
-    ShardBase &s = c->sh[0];
-    LAMCHK(set_dev(c, s));
-    return dispatch(c, [&](auto impl) -> int {
-        using I = decltype(impl);
-        using TA = typename ImplTraits<I>::TA;
-        using TV = typename ImplTraits<I>::TV;
-        if constexpr (!std::is_same<TA, TV>::value) {
-            return 0;
-        } else {
-            // the launch's GEMV phase is the tile body of the 2-rows-per-4-wave-workgroup shape (variant 10): it is bit-identical to
-            // the two-launch chain only when that chain runs the same shape
-            if (!I::fast_ok(c) || I::variant(c) != 10 || s.nrows != c->n || (c->n % 2) != 0 || (c->n % I::VEC) != 0) return 0;
-            int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cg_persist_kernel<TA, TV>, kBlock, 0) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s.dev) != hipSuccess) {
-                (void)hipGetLastError();
-                return 0;
-            }
-            if (c->opt_assume_cus > 0) cus = (int)c->opt_assume_cus;
-            const int64_t npairs = (int64_t)(c->n / 2);
-            const int64_t ntiles = (int64_t)((c->n + 4095) / 4096);
-            int64_t W = std::min<int64_t>({(int64_t)std::min(per_cu, 8) * cus - 1, npairs, (int64_t)kPersistLinesMax});
-            W = W / ntiles * ntiles;
-            if (W < (int64_t)s.vec_blocks || W < 64) return 0;      // too few resident workgroups: two-launch form
-            if (c->persist_bc == nullptr) {
-                HIPCHK(c, hipMalloc((void **)&c->persist_bc, (size_t)(kVecBlocksMax + kPersistLinesMax) * sizeof(BcastLine)));
-                HIPCHK(c, hipMemset(c->persist_bc, 0, (size_t)(kVecBlocksMax + kPersistLinesMax) * sizeof(BcastLine)));
-                HIPCHK(c, hipMalloc((void **)&c->persist_ticks, 2 * sizeof(unsigned long long)));
-                HIPCHK(c, hipHostMalloc((void **)&c->persist_ticks_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-            }
-            HIPCHK(c, hipMemsetAsync(c->persist_ticks, 0, 2 * sizeof(unsigned long long), s.stream));
-            c->persist_W = (int)W;
-            c->persist_active = true;
-            return 0;
-        }
-    });
-}
-
-// `count` iterations starting at k_first in ONE launch
-int enqueue_persist_chunk(lam_hip_ctx *c, int k_first, int count, double rel_error)
-{
-    return dispatch(c, [&](auto impl) -> int {
-        using I = decltype(impl);
-        using TA = typename ImplTraits<I>::TA;
-        using TV = typename ImplTraits<I>::TV;
-        if constexpr (!std::is_same<TA, TV>::value) {
-            return fail(c, LAM_HIP_EINVAL, "persistent launch: not for this dtype");
-        } else {
-            ShardBase &s = c->sh[0];
-            LAMCHK(set_dev(c, s));
-            PersistArgs<TA, TV> a;
-            a.A = (const TA *)s.A; a.n = c->n; a.lda = c->lda;
-            a.pbuf[0] = (TV *)s.p; a.pbuf[1] = (TV *)s.tmp;
-            a.r = (TV *)s.r; a.x = (TV *)s.x; a.Ap = (TV *)s.Ap;
-            a.part_gemv = s.part_gemv; a.part_vec = s.part_vec;
-            a.sc = s.sc; a.k_first = k_first; a.k_count = count; a.rel_error = rel_error;
-            a.host_flags = (volatile int *)s.host_flags; a.host_err = c->direct_err;
-            a.bc_pap = c->persist_bc; a.bc_rr = c->persist_bc + kVecBlocksMax;
-            a.W = c->persist_W; a.vec_blocks = s.vec_blocks;
-            a.npairs = (uint32_t)(c->n / 2); a.ntiles = (uint32_t)((c->n + 4095) / 4096);
-            a.seq_base = c->seq_base;
-            c->seq_span = std::max<uint64_t>(c->seq_span, (uint64_t)(k_first + count));
-            a.ticks = c->persist_ticks;
-            hipLaunchKernelGGL((cg_persist_kernel<TA, TV>), dim3(c->persist_W + 1), dim3(kBlock), 0, s.stream, a);
-            LAUNCHED(c);
-            return 0;
-        }
-    });
-}
-#else
-int decide_persistent(lam_hip_ctx *c) { c->persist_active = false; return 0; }
-#endif  // LAM_TUNING_VARIANTS
 
 int do_cg_init(lam_hip_ctx *c)
 {
@@ -125,7 +38,6 @@ int do_cg_init(lam_hip_ctx *c)
     }
     if (c->fuse_active)
         for (auto &sh_ : c->sh) LAMCHK(ensure_mail(c, sh_, nullptr));
-    LAMCHK(decide_persistent(c));
     if (c->exchange1_ok()) return do_cg_init_exchange1(c);
     c->cg_exchange1 = false;
     return dispatch(c, [&](auto impl) -> int {
@@ -155,9 +67,7 @@ int do_cg_init(lam_hip_ctx *c)
 
 // ---- the general iteration, one shard at a time -------------------------------------------------------------------
 // Four phases per shard; between two phases every shard must have ISSUED the previous one (its event records are
-// what the next phase's stream waits refer to).  One host thread: phase by phase over all shards.  One host thread
-// per shard (option "host_threads", the shape of the reference's OpenMP-thread-per-device loop,
-// ConjugateGradient_MultiGPUS_CUDA.cu:337-378): a host barrier between the phases (iterate_threaded).
+// what the next phase's stream waits refer to).  One host thread: phase by phase over all shards.
 //   A  GEMV (+ partial p.Ap; the product step's helpers are lam_exchange.h's) and its post
 //   B  wait for the peers' p.Ap; x, r update (+ partial r.r); post
 //   C  wait for the peers' r.r; stop test + p update into every replica; post        D  wait for the peers' p slices
@@ -250,19 +160,16 @@ int enqueue_iteration_body(lam_hip_ctx *c, int k, double rel_error, int slot)
             LAMCHK(phase_gemv<I>(c, s, k, slot));
         }
         c->gather_pending = false;
-        LAMCHK(hub_join(c, 0));
         for (auto &s : c->sh) {
             LAMCHK(set_dev(c, s));
             LAMCHK(phase_xr<I>(c, s, k, rel_error));
         }
         if (c->fuse_active) return 0;
-        LAMCHK(hub_join(c, 1));
         for (auto &s : c->sh) {
             LAMCHK(set_dev(c, s));
             LAMCHK(phase_p<I>(c, s, k, rel_error));
         }
         if (c->rank_mode) return gather_p_rank(c);
-        LAMCHK(hub_join(c, 2));
         for (auto &s : c->sh) {
             LAMCHK(set_dev(c, s));
             LAMCHK(gather_wait(c, s));
@@ -352,36 +259,6 @@ int await_progress(lam_hip_ctx *c, ShardBase &s0, int target, Progress *out, boo
     }
 }
 
-#ifdef LAM_TUNING_VARIANTS
-// TUNING BUILD ONLY (option "host_threads").
-// Host barrier of the per-shard enqueue threads.  wait(flags) returns the OR of the flags every thread brought to
-// THIS barrier, so all threads leave the loop at the same barrier (a flag raised between two barriers is seen by
-// everybody at the next one, by nobody before).
-struct HostBarrier {
-    explicit HostBarrier(int n_) : n(n_) {}
-    const int n;
-    std::atomic<int> count{0}, gen{0}, acc{0};
-    int result[2] = {0, 0};
-    int wait(int flags)
-    {
-        if (flags) acc.fetch_or(flags, std::memory_order_acq_rel);
-        const int g = gen.load(std::memory_order_acquire);
-        if (count.fetch_add(1, std::memory_order_acq_rel) + 1 == n) {
-            result[(g + 1) & 1] = acc.exchange(0, std::memory_order_acq_rel);
-            count.store(0, std::memory_order_relaxed);
-            gen.store(g + 1, std::memory_order_release);
-        } else {
-            unsigned spins = 0;
-            while (gen.load(std::memory_order_acquire) == g) {
-                if (++spins > 20000u) sched_yield(); else __builtin_ia32_pause();
-            }
-        }
-        return result[(g + 1) & 1];
-    }
-};
-#endif
-
-
 // GEMV device time of the iteration that used ring slot `slot`, per local shard, if that iteration was timed; for shard 0 also the
 // time of its exchange steps (xt_begin / xt_end pairs)
 struct IterTimes {
@@ -446,76 +323,4 @@ static int lag_check(lam_hip_ctx *c, ShardBase &s0, int k)
     return (pr.stop_at != 0 && (pr.stop_at <= k - kLag || level_stop)) ? 1 : 0;
 }
 
-#ifdef LAM_TUNING_VARIANTS
-// TUNING BUILD ONLY (option "host_threads": 0.30 ms of host time per iteration at 8 shards where the plain loop takes 0.59 and the
-// gather-Ap exchange 0.15 -- the runtime serialises much of it).
-// One process, several shards: every shard is enqueued by a host thread of its own (the reference drives each device
-// from its own OpenMP thread, ConjugateGradient_MultiGPUS_CUDA.cu:264-283,337-378).  With one thread for P shards an
-// iteration costs the host 3P launches + ~3P event records + 3P(P-1) stream waits one after the other; here they are
-// issued P-wide, with a host barrier between the phases (a stream wait must follow the record it refers to).
-static int iterate_threaded(lam_hip_ctx *c, int iters, int k_first, double rel_error, int *enq_out, IterTimes *times)
-{
-    const int L = (int)c->sh.size();
-    HostBarrier bar(L);
-    std::vector<int> rcs(L, 0);
-    int enq = 0;
-    std::atomic<int> go{0};                         // 0: wait, 1: run, 2: cancelled (a thread could not be created)
-    auto worker = [&](int q) {
-        while (go.load(std::memory_order_acquire) == 0) sched_yield();
-        if (go.load(std::memory_order_acquire) == 2) return;
-        ShardBase &s = c->sh[q];
-        int rc = set_dev(c, s);
-        auto phase = [&](auto &&fn) {               // run one phase unless this thread has already failed
-            if (rc == 0) rc = fn();
-            return bar.wait(rc != 0 ? 1 : 0);
-        };
-        for (int i = 0; i < iters; i++) {
-            const int k = k_first + i, slot = i % kLag;
-            if (i >= kLag) {
-                int flags = rc != 0 ? 1 : 0;
-                if (q == 0 && rc == 0) {
-                    const int d = lag_check(c, s, k);
-                    if (d < 0) { rc = d; flags |= 1; }
-                    else if (d != 0) flags |= 2;
-                    else harvest_shard(s, 0, slot, times);
-                }
-                if (bar.wait(flags) != 0) break;
-            }
-            const double te = q == 0 ? now_s() : 0.0;
-            // with the hub, thread 0 issues the join between two barriers (everybody's post before it, everybody's wait after it)
-            auto join = [&](int which) {
-                if (!hub_active(c)) return 0;
-                if (q == 0 && rc == 0) rc = hub_join(c, which);
-                return bar.wait(rc != 0 ? 1 : 0);
-            };
-            if (phase([&] { return dispatch(c, [&](auto impl) -> int { return phase_gemv<decltype(impl)>(c, s, k, slot); }); })) break;
-            if (join(0)) break;
-            if (phase([&] { return dispatch(c, [&](auto impl) -> int { return phase_xr<decltype(impl)>(c, s, k, rel_error); }); })) break;
-            if (join(1)) break;
-            if (phase([&] { return dispatch(c, [&](auto impl) -> int { return phase_p<decltype(impl)>(c, s, k, rel_error); }); })) break;
-            if (join(2)) break;
-            if (rc == 0) rc = gather_wait(c, s);       // refers to records issued before the last barrier: no barrier needed
-            if (q == 0) { enq++; c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9); }
-        }
-        rcs[q] = rc;
-    };
-    std::vector<std::thread> th;
-    th.reserve(L);
-    try {
-        for (int q = 1; q < L; q++) th.emplace_back(worker, q);
-    } catch (...) {
-        // no exception may cross the C ABI, and the threads that did start must not wait at a barrier for ever
-        go.store(2, std::memory_order_release);
-        for (auto &t : th) t.join();
-        return fail(c, LAM_HIP_ENOMEM, "could not start the per-shard enqueue threads (option host_threads)");
-    }
-    go.store(1, std::memory_order_release);
-    worker(0);
-    for (auto &t : th) t.join();
-    *enq_out = enq;
-    for (int q = 0; q < L; q++)
-        if (rcs[q] != 0) return rcs[q];
-    return 0;
-}
-#endif  // LAM_TUNING_VARIANTS
 }  // namespace

@@ -17,17 +17,17 @@
 //   * the vector step's recurrence -- alpha, the x / r sweep, the gathered p.Ap, beta and the stop test, the p sweep -- is written
 //     ONCE, as the device helpers cg_alpha, sweep_xr, gathered_pap, cg_decide, sweep_p and sweep_p_slice at the head of the
 //     section "vector kernels".  Its six kernels (two kernels or one launch, on sliced or on full-length vectors) only say which
-//     workgroup reduces, computes or waits, where p.Ap and r.r come from and which elements a thread sweeps; the tuning build's
-//     cg_persist_kernel shares cg_decide.  That the forms agree bit for bit holds by construction.
+//     workgroup reduces, computes or waits, where p.Ap and r.r come from and which elements a thread sweeps.  That the forms agree
+//     bit for bit holds by construction.
 //   * all reductions are two-stage and fixed-order (no floating-point atomics): results are
 //     bit-reproducible run to run and identical on every shard.
 //   * GEMV is HBM-bound (0.25 flop/B in fp64).  Production shape (gemv_coop_kernel): the 4 waves of a
 //     workgroup stream the same 2 matrix rows with 16-byte non-temporal loads, 4 KiB contiguous per row
 //     per super-step; the matching 4096-column tile of p is staged once per workgroup in LDS; lane
 //     partials are combined with wave64 shuffles and across waves through LDS.  gemv_tile_kernel (one
-//     group of R rows per wave) is the production shape for bf16 storage and carries the tuning
-//     variants; gemv_generic_kernel handles any N / alignment; gemv_mfma_bf16_kernel is the MFMA
-//     experiment (slower, kept for the record).  A launch can cover one or two column panels and
+//     group of 4 rows per wave) is the production shape for bf16 storage; gemv_generic_kernel handles
+//     any N / alignment; gemv_mfma_bf16_kernel is the MFMA experiment (slower, tuning build only: bench.py
+//     measures it beside the product kernel).  A launch can cover one or two column panels and
 //     accumulate, which is how the rank mode overlaps the all-gather of p with its own-slice panel.
 //   * the *_full_kernel family implements the single-exchange iteration (gather of Ap, full-length r and p on every shard);
 //     symv_*_kernel implement the opt-in symmetric product (every pair {i, j} read once: the upper triangle on one shard,
@@ -486,21 +486,20 @@ __device__ __forceinline__ void store_y(const GemvArgs<TA, TV> &a, uint64_t row,
 
 // Fast path: n % (16/sizeof(TA)) == 0, A and p 16-byte aligned.
 //   workgroup = 4 waves, wave w owns rows (4*blockIdx+w)*R .. +R-1, all n columns.
-//   TILE elements of p live in LDS at a time.
-//   USE_LDS = false reads p straight from global memory (L2-resident) instead -- kept as a tuning
-//   variant; ROT = false visits the tiles in natural order.
-template <typename TA, typename TV, int R, int TILE, bool NT, int UNROLL, bool USE_LDS = true, bool ROT = true>
+//   TILE elements of p live in LDS at a time; a workgroup starts at tile blockIdx % ntiles (rotated order).
+template <typename TA, typename TV, bool NT>
 __global__ void __launch_bounds__(kBlock)
 gemv_tile_kernel(GemvArgs<TA, TV> a)
 {
     using MV = MatVec<TA>;
     using avec_t = typename MV::vec_t;
+    constexpr int R = 4, TILE = 4096, UNROLL = 4;
     constexpr int VEC = MV::N;
     constexpr int STEP = 64 * VEC;          // columns one wave instruction covers
     static_assert(TILE % STEP == 0, "tile must be a whole number of wave steps");
     constexpr int STEPS = TILE / STEP;
 
-    __shared__ __attribute__((aligned(16))) TV s_p[USE_LDS ? TILE : 4];
+    __shared__ __attribute__((aligned(16))) TV s_p[TILE];
     __shared__ double s_red[kWaves];
 
     if (a.sc != nullptr && a.sc->stop) return;
@@ -524,13 +523,12 @@ gemv_tile_kernel(GemvArgs<TA, TV> a)
 
     const uint32_t ntiles0 = (uint32_t)((a.seg_end[0] - a.seg_begin[0] + TILE - 1) / TILE);
     const uint32_t ntiles = ntiles0 + (a.nseg > 1 ? (uint32_t)((a.seg_end[1] - a.seg_begin[1] + TILE - 1) / TILE) : 0u);
-    uint32_t tt = ROT ? blockIdx.x % ntiles : 0;     // rotated start
+    uint32_t tt = blockIdx.x % ntiles;     // rotated start
     for (uint32_t t = 0; t < ntiles; t++) {
         const bool second = tt >= ntiles0;
         const uint64_t c0 = second ? a.seg_begin[1] + (uint64_t)(tt - ntiles0) * TILE : a.seg_begin[0] + (uint64_t)tt * TILE;
         const uint64_t cend = second ? a.seg_end[1] : a.seg_end[0];
         const uint32_t cols = (uint32_t)((cend - c0 < (uint64_t)TILE) ? (cend - c0) : (uint64_t)TILE);
-        if constexpr (USE_LDS) {
         __syncthreads();                              // previous tile fully consumed
         // stage p[c0 .. c0+cols) -- 16-byte loads, cols is a multiple of VEC (>= 16 B of TV too)
         {
@@ -545,8 +543,7 @@ gemv_tile_kernel(GemvArgs<TA, TV> a)
             for (uint32_t i = cols + tid; i < (uint32_t)TILE && i < (cols + STEP - 1) / STEP * STEP; i += kBlock) s_p[i] = (TV)0;
         }
         __syncthreads();
-        }
-        const TV *pt = USE_LDS ? (const TV *)s_p : a.p + c0;
+        const TV *pt = s_p;
 
         if (cols == TILE) {
 #pragma unroll UNROLL
@@ -569,7 +566,7 @@ gemv_tile_kernel(GemvArgs<TA, TV> a)
             // Ragged last tile of a segment (N not a multiple of TILE: 18 % of the columns at N=10000): the SAME
             // streaming body over ceil(cols / STEP) steps.  Lanes past the end of the segment read the row's last
             // vector again (address clamped: in bounds) and multiply a ZERO in its place (and a zero of p: the p tile is
-            // zero-filled behind `cols` (LDS) or masked (p from L2)), so they add exactly +0 -- also when that last vector
+            // zero-filled behind `cols`), so they add exactly +0 -- also when that last vector
             // holds +-Inf or NaN, which times the zero of p alone would turn into a NaN row sum.  No second
             // code path with its own registers: round 2's separately unrolled ragged body doubled the kernels' VGPRs
             // (fp32 54 -> 98, bf16 104 -> 256: occupancy 8 -> 4 and 4 -> 1) and the full-tile path paid for it.
@@ -586,7 +583,7 @@ gemv_tile_kernel(GemvArgs<TA, TV> a)
                 }
                 TV pv[VEC];
 #pragma unroll
-                for (int i = 0; i < VEC; i++) pv[i] = USE_LDS ? pt[col + i] : (col < cols ? pt[col + i] : (TV)0);
+                for (int i = 0; i < VEC; i++) pv[i] = pt[col + i];
 #pragma unroll
                 for (int r = 0; r < R; r++)
 #pragma unroll
@@ -626,12 +623,13 @@ gemv_tile_kernel(GemvArgs<TA, TV> a)
 // 4th 1-KiB step, so a workgroup reads 4 KiB contiguous per row per super-step and the chip has
 // 4x fewer concurrent row streams than the wave-per-row shape (DRAM page locality experiment).
 // The row sums are combined across waves through LDS in a fixed order.
-template <typename TA, typename TV, int R, int TILE, bool NT, int UNROLL, int WAVES = 4>
+template <typename TA, typename TV, int R, bool NT, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64)
 gemv_coop_kernel(GemvArgs<TA, TV> a)
 {
     using MV = MatVec<TA>;
     using avec_t = typename MV::vec_t;
+    constexpr int TILE = 4096, UNROLL = 4;
     constexpr int VEC = MV::N;
     constexpr int STEP = 64 * VEC;
     static_assert(TILE % (STEP * WAVES) == 0, "tile must be a whole number of workgroup super-steps");
@@ -762,148 +760,9 @@ gemv_coop_kernel(GemvArgs<TA, TV> a)
 }
 
 // ==== From here to the matching #endif: TUNING BUILD ONLY (-DLAM_TUNING_VARIANTS, `make tuning` -> liblam_hip_tuning.so).
-// Experiments that were built, tested, measured and did not win: the grouped cooperative-row
-// probe, the MFMA-fed bf16 GEMV.  The product library does not carry them.
+// The MFMA-fed bf16 GEMV: built, tested, measured, slower than the VALU kernel; bench.py measures it
+// beside the product kernel for BASELINE configs[3].  The product library does not carry it.
 #ifdef LAM_TUNING_VARIANTS
-// One p tile's worth of the cooperative-row stream as a function: R rows, columns [c0, c0 + cols) of each, accumulated
-// into acc[R] -- statement for statement the tile body of gemv_coop_kernel (which keeps its own inline copy: moving it
-// behind this call changed the production kernels' register allocation), so that cg_persist_kernel adds a row's
-// products in exactly the same order.  rowp[r] points at the row's element `woff` (this lane's column inside a
-// super-step); s_p holds p[c0 ...] with zeros behind `cols` up to the next whole super-step.
-template <typename TA, typename TV, int R, int TILE, bool NT, int UNROLL, int WAVES>
-__device__ __forceinline__ void coop_stream_tile(const TA *const (&rowp)[R], uint64_t c0, uint32_t cols, const TV *s_p, uint32_t woff, TV (&acc)[R])
-{
-    using MV = MatVec<TA>;
-    using avec_t = typename MV::vec_t;
-    constexpr int VEC = MV::N;
-    constexpr int STEP = 64 * VEC;
-    constexpr int WSTEPS = TILE / (STEP * WAVES);
-    if (cols == TILE) {
-#pragma unroll UNROLL
-        for (int s = 0; s < WSTEPS; s++) {
-            avec_t av[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const avec_t *src = reinterpret_cast<const avec_t *>(rowp[r] + c0 + (uint64_t)s * (STEP * WAVES));
-                av[r] = NT ? __builtin_nontemporal_load(src) : *src;
-            }
-            TV pv[VEC];
-#pragma unroll
-            for (int i = 0; i < VEC; i++) pv[i] = s_p[s * (STEP * WAVES) + woff + i];
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int i = 0; i < VEC; i++) acc[r] = fma_tv((TV)MV::get(av[r], i), pv[i], acc[r]);
-        }
-    } else {
-        const int nsteps = (int)((cols + STEP * WAVES - 1) / (STEP * WAVES));
-#pragma unroll UNROLL
-        for (int s = 0; s < nsteps; s++) {
-            const uint32_t col = (uint32_t)s * (STEP * WAVES) + woff;
-            avec_t av[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const avec_t *src = col < cols ? reinterpret_cast<const avec_t *>(rowp[r] + c0 + (uint64_t)s * (STEP * WAVES))
-                                               : reinterpret_cast<const avec_t *>(kZeroVec16);
-                av[r] = NT ? __builtin_nontemporal_load(src) : *src;
-            }
-            TV pv[VEC];
-#pragma unroll
-            for (int i = 0; i < VEC; i++) pv[i] = s_p[col + i];
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int i = 0; i < VEC; i++) acc[r] = fma_tv((TV)MV::get(av[r], i), pv[i], acc[r]);
-        }
-    }
-}
-
-// Tuning probe: the cooperative-row GEMV with GROUP consecutive row pairs per workgroup that
-// share every staged p tile -- does halving / quartering the number of workgroups (launches, epilogues, staged tiles) lift
-// the short-row sizes?  Same per-row arithmetic; the rotated tile order starts at blockIdx (not pair index) % tiles, so the
-// bits differ from the production kernel's.
-template <typename TA, typename TV, int GROUP>
-__global__ void __launch_bounds__(kBlock)
-gemv_coop_group_kernel(GemvArgs<TA, TV> a)
-{
-    using MV = MatVec<TA>;
-    constexpr int VEC = MV::N, R = 2, TILE = 4096, WAVES = 4, UNROLL = 4;
-    constexpr int STEP = 64 * VEC;
-    __shared__ __attribute__((aligned(16))) TV s_p[TILE];
-    __shared__ TV s_part[GROUP][R][WAVES];
-    __shared__ double s_dot[GROUP * R];
-    __shared__ double s_red[kWaves];
-    if (a.sc != nullptr && a.sc->stop) return;
-    if (is_reducer_block(a.fin)) { reduce_partials(a.partial, (int)gridDim.x - 1, a.fin, s_red); return; }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t n = a.n;
-    const uint64_t row_first = (uint64_t)blockIdx.x * R * GROUP;
-    const uint32_t woff = (uint32_t)wave * STEP + (uint32_t)lane * VEC;
-    TV acc[GROUP][R];
-#pragma unroll
-    for (int g = 0; g < GROUP; g++)
-#pragma unroll
-        for (int r = 0; r < R; r++) acc[g][r] = (TV)0;
-    const uint32_t ntiles = (uint32_t)((n + TILE - 1) / TILE);
-    uint32_t tt = blockIdx.x % ntiles;
-    for (uint32_t t = 0; t < ntiles; t++) {
-        const uint64_t c0 = (uint64_t)tt * TILE;
-        const uint32_t cols = (uint32_t)((n - c0 < (uint64_t)TILE) ? (n - c0) : (uint64_t)TILE);
-        __syncthreads();
-        {
-            constexpr int PV = 16 / sizeof(TV);
-            typedef TV pvec_t __attribute__((ext_vector_type(PV)));
-            const pvec_t *src = reinterpret_cast<const pvec_t *>(a.p + c0);
-            pvec_t *dst = reinterpret_cast<pvec_t *>(s_p);
-            const uint32_t nv = cols / PV;
-            for (uint32_t i = tid; i < nv; i += kBlock) dst[i] = src[i];
-            for (uint32_t i = nv * PV + tid; i < cols; i += kBlock) s_p[i] = a.p[c0 + i];
-            for (uint32_t i = cols + tid; i < (uint32_t)TILE && i < (cols + STEP * WAVES - 1) / (STEP * WAVES) * (STEP * WAVES); i += kBlock) s_p[i] = (TV)0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < GROUP; g++) {
-            const TA *rowp[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                uint64_t row = row_first + (uint64_t)g * R + r;
-                if (row >= a.nrows) row = a.nrows - 1;
-                rowp[r] = a.A + row * a.lda + woff;
-            }
-            coop_stream_tile<TA, TV, R, TILE, true, UNROLL, WAVES>(rowp, c0, cols, s_p, woff, acc[g]);
-        }
-        tt = (tt + 1 == ntiles) ? 0 : tt + 1;
-    }
-#pragma unroll
-    for (int g = 0; g < GROUP; g++)
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const TV sacc = wave_sum(acc[g][r]);
-            if (lane == 0) s_part[g][r][wave] = sacc;
-        }
-    __syncthreads();
-    if (tid < GROUP * R) {
-        const int g = tid / R, r = tid % R;
-        const uint64_t row = row_first + (uint64_t)g * R + r;
-        double d = 0.0;
-        if (row < a.nrows) {
-            TV sum = s_part[g][r][0];
-#pragma unroll
-            for (int wv = 1; wv < WAVES; wv++) sum += s_part[g][r][wv];
-            store_y(a, row, sum);
-            d = (double)sum * (double)a.p[a.row0 + row];
-        }
-        s_dot[tid] = d;
-    }
-    if (a.partial != nullptr) {
-        __syncthreads();
-        double t = 0.0;
-        if (tid == 0)
-            for (int i = 0; i < GROUP * R; i++) t += s_dot[i];
-        publish_partial(t, a.partial, a.fin);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // MFMA experiment for the bf16-storage GEMV (BASELINE configs[3]): can the matrix cores take the
 // widening + FMA work off the VALU?  A wave loads 1 KiB = 512 contiguous bf16 of ONE matrix row
@@ -1048,7 +907,7 @@ gemv_mfma_bf16_kernel(GemvArgs<__hip_bfloat16, float> a)
     }
 }
 
-#endif  // LAM_TUNING_VARIANTS (grouped cooperative rows, MFMA-fed bf16 GEMV)
+#endif  // LAM_TUNING_VARIANTS (MFMA-fed bf16 GEMV)
 
 // ---------------------------------------------------------------------------------------------
 // Symmetric product (option "symmetric", single shard): y = A p reading only the UPPER triangle.
@@ -2008,319 +1867,6 @@ update_full_fused_kernel(const char *__restrict__ gathered, uint64_t stride_byte
     if (d.stop) return;
     sweep_p(d.beta, first, stride, n, (const TV *)r_full, (const TV *)p_full, [&](uint64_t i, TV pi) { p_full[i] = pi; });
 }
-
-#ifdef LAM_TUNING_VARIANTS
-// ---------------------------------------------------------------------------------------------
-// TUNING BUILD ONLY.
-// Whole-iteration persistent launch (option "persistent"; one shard, fp64 / fp32, N a multiple of the vector width).
-// EXPERIMENT, off by default; DESIGN.md section 6 has the measurement.
-//
-// One launch runs `k_count` CG iterations.  The grid is W worker workgroups + ONE reducer workgroup, all resident at
-// once (the host checks the occupancy before it uses this kernel).  Per iteration:
-//   * GEMV.  Worker w owns the row pairs q = w, w + W, w + 2W, ... (W is a multiple of the number of p tiles, so all
-//     of them start their rotated tile order at the same tile) and handles them in groups of kPersistGroup: one p tile
-//     is staged in LDS ONCE per group and every pair of the group streams its two rows against it with the tile body
-//     of gemv_coop_kernel (coop_stream_tile) -- a row's products are added in exactly the order of the two-launch form.
-//     Ap goes to memory with agent-scope (write-through) stores; the pair's partial of p.Ap goes to part_gemv[q], the
-//     same slot and value the two-launch form writes.
-//   * p is never "updated" in a phase of its own: from the second iteration of a launch on, a tile of
-//     p_k = r_k + beta_k p_{k-1} is formed WHILE IT IS STAGED, from r and the last explicitly stored p (two 16-byte
-//     sc1 loads and one FMA per element instead of one load; a quarter of the staging the two-launch GEMV does, because
-//     of the groups).  That removes the third grid-wide dependency of an iteration: two hand-overs remain.
-//   * hand-over 1: the reducer workgroup sums the partials in the order of block_sum_array (bit-identical p.Ap) while
-//     the GEMV is still running, and broadcasts the total to the first `vec_blocks` workers, each on a line of its own.
-//   * vector step on those workers, with the element -> (workgroup, thread) mapping of update_xr_kernel: p_k[i] is
-//     formed once more (and stored: it is the "last explicit p" of the next iteration, in the other of two buffers),
-//     x += alpha p, r -= alpha Ap, partials of r.r to part_vec[cb].
-//   * hand-over 2: the reducer sums them (bit-identical r.r) and broadcasts to ALL workers: beta, the stop test (every
-//     workgroup takes the same decision from the same bits), and the next GEMV starts -- no kernel boundary, no launch
-//     ramp.  Worker 0 keeps CgScalars and the host's progress word up to date.
-//   * on exit the explicit p of the two-launch form is materialised in pbuf[0], so either form can continue the solve.
-// Everything handed over inside the launch is written with sc1 stores that the writing wave drains (s_waitcnt vmcnt(0))
-// before the workgroup's flag goes out, and read with sc1 loads (MI355X_MICROARCH.md, "Valid forms"); every wait is
-// bounded (SpinGuard) and reports through host_err.
-// ---------------------------------------------------------------------------------------------
-constexpr int kPersistGroup = 4;
-
-template <typename TA, typename TV>
-struct PersistArgs {
-    const TA *A;
-    uint64_t n;
-    uint64_t lda;                 // row pitch of A in elements
-    TV *pbuf[2];                  // [0] the shard's p (explicit on entry and on exit), [1] a scratch vector
-    TV *r, *x, *Ap;
-    double *part_gemv;            // [npairs], armed with the sentinel
-    double *part_vec;             // [vec_blocks], armed
-    CgScalars *sc;
-    int k_first, k_count;
-    double rel_error;
-    volatile int *host_flags;
-    int *host_err;
-    BcastLine *bc_pap;            // [vec_blocks]
-    BcastLine *bc_rr;             // [W]
-    int W, vec_blocks;
-    uint32_t npairs, ntiles;
-    unsigned long long seq_base;  // hand-over number of iteration k = seq_base + k (grows over the life of the context)
-    unsigned long long *ticks;    // [0] += constant-rate ticks (100 MHz) spent in GEMV phases, [1] += phases
-};
-
-template <typename T> __device__ __forceinline__ T ld_agent(const T *p);
-template <> __device__ __forceinline__ double ld_agent<double>(const double *p)
-{
-    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-template <> __device__ __forceinline__ float ld_agent<float>(const float *p)
-{
-    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-template <typename T> __device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// 16-byte sc1 load (L1-bypassing, what a hand-over inside a launch needs) as issued / waited-for pair: the compiler does
-// not know the load is asynchronous, so every register it fills is tied to the wait below before anything reads it
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4_t ld16_sc1_issue(const void *p)
-{
-    u32x4_t v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
-__device__ __forceinline__ void ld16_wait(u32x4_t &a, u32x4_t &b, u32x4_t &c, u32x4_t &d, u32x4_t &e, u32x4_t &f, u32x4_t &g, u32x4_t &h)
-{
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : : "memory");
-}
-
-// bcast_wait for the persistent launch.  There a worker waits for a WHOLE GEMV phase of the slowest worker (tens of
-// microseconds to milliseconds), and a thousand workgroups wait at once: the abort word in pinned host memory (a PCIe read)
-// and the clock are looked at once every 8192 failed polls (the first version read it every 256 polls and once per iteration
-// in every thread: ~650 us per iteration at every N, all of it PCIe reads).  Polls back off from s_sleep 1 to s_sleep 8 after 512 of them.
-__device__ __forceinline__ double persist_wait(const BcastLine *line, unsigned long long seq, int *host_err, double *s_red)
-{
-    const MailSlot *slot = &line->s;
-    double v = 0.0;
-    if (threadIdx.x == 0) {
-        unsigned polls = 0, seen;
-        unsigned long long t0 = 0;
-        while (!handover_try_load<__HIP_MEMORY_SCOPE_AGENT>(slot, seq, &v, &seen)) {
-            if ((++polls & 8191u) == 0) {
-                const unsigned long long now = (unsigned long long)clock64();
-                if (t0 == 0) t0 = now | 1ull;
-                if (*(volatile int *)host_err != 0) break;
-                if (now - t0 > kSpinTimeoutCycles) {
-                    host_err[1] = -1; host_err[2] = (int)(unsigned)seq; host_err[3] = (int)seen;
-                    host_err[4] = (int)(seq >> 32); host_err[5] = 0;
-                    *(volatile int *)host_err = 4;
-                    break;
-                }
-            }
-            if (polls < 512u) __builtin_amdgcn_s_sleep(1); else __builtin_amdgcn_s_sleep(8);
-        }
-    }
-    return block_sum(v, s_red);
-}
-
-template <typename TA, typename TV>
-__global__ void __launch_bounds__(kBlock, 4)      // 4 waves per SIMD = 4 workgroups per CU (what the LDS tile allows in fp64): <= 128 VGPRs
-cg_persist_kernel(PersistArgs<TA, TV> a)
-{
-    static_assert(std::is_same<TA, TV>::value, "persistent launch: matrix and vectors of one type");
-    using MV = MatVec<TA>;
-    constexpr int VEC = MV::N, R = 2, TILE = 4096, WAVES = 4, UNROLL = 4, G = kPersistGroup;
-    constexpr int STEP = 64 * VEC;
-    constexpr int PV = 16 / sizeof(TV);
-    typedef TV pvec_t __attribute__((ext_vector_type(PV)));
-
-    __shared__ __attribute__((aligned(16))) TV s_p[TILE];
-    __shared__ TV s_part[G][R][WAVES];
-    __shared__ double s_dot[G * R];
-    __shared__ double s_red[kWaves];
-
-    if (a.sc->stop) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w = (int)blockIdx.x;
-    const uint64_t n = a.n;
-    const double bb = a.sc->bb;
-
-    if (w == a.W) {
-        // ---- the reducer workgroup: both hand-overs of every iteration
-        unsigned long long t_prev = wall_clock64();
-        for (int it = 0; it < a.k_count; it++) {
-            const unsigned long long seq = a.seq_base + (unsigned)(a.k_first + it);
-            const double pAp = reduce_partials_sum(a.part_gemv, (int)a.npairs, s_red, a.host_err);
-            const unsigned long long t_gemv_end = wall_clock64();
-            bcast_post(a.bc_pap, a.vec_blocks, pAp, seq);
-            const double rr_new = reduce_partials_sum(a.part_vec, a.vec_blocks, s_red, a.host_err);
-            bcast_post(a.bc_rr, a.W, rr_new, seq);
-            if (tid == 0) { a.ticks[0] += t_gemv_end - t_prev; a.ticks[1] += 1; }
-            t_prev = wall_clock64();
-            if (sqrt(rr_new / bb) < a.rel_error) return;
-            if (!(rr_new == rr_new)) return;              // a bounded wait expired somewhere (NaN total): the launch drains
-        }
-        return;
-    }
-
-    const uint32_t woff = (uint32_t)wave * STEP + (uint32_t)lane * VEC;
-    double rr_old = a.sc->rr[(a.k_first + 1) & 1];
-    TV beta = (TV)0;
-    int cur = 0;                                  // pbuf[cur]: the last explicitly stored p
-    for (int it = 0; it < a.k_count; it++) {
-        const int k = a.k_first + it;
-        const unsigned long long seq = a.seq_base + (unsigned)k;
-        const bool direct = it == 0;              // p_{k-1} is explicit in pbuf[cur]; else p_{k-1} = r + beta pbuf[cur]
-        const TV *pold = a.pbuf[cur];
-        TV *pdst = a.pbuf[cur ^ 1];
-
-        // ---- GEMV over the pairs this worker owns, kPersistGroup at a time
-        for (uint32_t q0 = (uint32_t)w; q0 < a.npairs; q0 += (uint32_t)(G * a.W)) {
-            TV acc[G][R];
-#pragma unroll
-            for (int g = 0; g < G; g++)
-#pragma unroll
-                for (int r = 0; r < R; r++) acc[g][r] = (TV)0;
-            const TA *const lane0 = a.A + woff;            // row pointers are rebuilt per (tile, pair): 16 registers less
-            uint32_t tt = (uint32_t)w % a.ntiles;          // == q % ntiles for every pair of this worker (W % ntiles == 0)
-            for (uint32_t t = 0; t < a.ntiles; t++) {
-                const uint64_t c0 = (uint64_t)tt * TILE;
-                const uint32_t cols = (uint32_t)((n - c0 < (uint64_t)TILE) ? (n - c0) : (uint64_t)TILE);
-                const uint32_t nv = cols / PV;
-                __syncthreads();                           // the previous tile is fully consumed
-                if (direct) {
-                    const pvec_t *src = reinterpret_cast<const pvec_t *>(pold + c0);
-                    pvec_t *dst = reinterpret_cast<pvec_t *>(s_p);
-                    for (uint32_t i = tid; i < nv; i += kBlock) dst[i] = src[i];
-                } else {
-                    // p_k = r_k + beta p_{k-1}, formed while it is staged (same expression as update_p_kernel)
-                    const char *rsrc = reinterpret_cast<const char *>(a.r + c0), *psrc = reinterpret_cast<const char *>(pold + c0);
-                    for (uint32_t base = 0; base < nv; base += 4 * kBlock) {
-                        u32x4_t rv[4], pv[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            uint32_t i = base + u * kBlock + tid;
-                            if (i >= nv) i = nv - 1;        // clamped: in bounds, result not stored
-                            rv[u] = ld16_sc1_issue(rsrc + (size_t)i * 16);
-                            pv[u] = ld16_sc1_issue(psrc + (size_t)i * 16);
-                        }
-                        ld16_wait(rv[0], rv[1], rv[2], rv[3], pv[0], pv[1], pv[2], pv[3]);
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            const uint32_t i = base + u * kBlock + tid;
-                            if (i < nv) {
-                                const pvec_t rr_ = __builtin_bit_cast(pvec_t, rv[u]), pp_ = __builtin_bit_cast(pvec_t, pv[u]);
-                                pvec_t o;
-#pragma unroll
-                                for (int e = 0; e < PV; e++) o[e] = rr_[e] + beta * pp_[e];
-                                reinterpret_cast<pvec_t *>(s_p)[i] = o;
-                            }
-                        }
-                    }
-                }
-                for (uint32_t i = cols + tid; i < (uint32_t)TILE && i < (cols + STEP * WAVES - 1) / (STEP * WAVES) * (STEP * WAVES); i += kBlock)
-                    s_p[i] = (TV)0;
-                __syncthreads();
-#pragma unroll
-                for (int g = 0; g < G; g++) {
-                    const uint64_t q = (uint64_t)q0 + (uint64_t)g * (uint64_t)a.W;
-                    if (q < a.npairs) {
-                        const TA *rowp[R];
-#pragma unroll
-                        for (int r = 0; r < R; r++) rowp[r] = lane0 + (q * R + r) * a.lda;
-                        coop_stream_tile<TA, TV, R, TILE, true, UNROLL, WAVES>(rowp, c0, cols, s_p, woff, acc[g]);
-                    }
-                }
-                tt = (tt + 1 == a.ntiles) ? 0 : tt + 1;
-            }
-            // epilogue of the group: row sums across the waves in the fixed order of gemv_coop_kernel
-#pragma unroll
-            for (int g = 0; g < G; g++)
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const TV sacc = wave_sum(acc[g][r]);
-                    if (lane == 0) s_part[g][r][wave] = sacc;
-                }
-            __syncthreads();
-            if (tid < G * R) {
-                const int g = tid / R, r = tid % R;
-                const uint64_t q = (uint64_t)q0 + (uint64_t)g * (uint64_t)a.W;
-                double d = 0.0;
-                if (q < a.npairs) {
-                    const uint64_t row = q * R + r;
-                    TV sum = s_part[g][r][0];
-#pragma unroll
-                    for (int wv = 1; wv < WAVES; wv++) sum += s_part[g][r][wv];
-                    st_agent(a.Ap + row, sum);
-                    const TV pk = direct ? pold[row] : (TV)(ld_agent(a.r + row) + beta * ld_agent(pold + row));
-                    d = (double)sum * (double)pk;
-                }
-                s_dot[tid] = d;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the Ap stores have left before the partial says so
-            __syncthreads();
-            if (tid < G) {
-                const uint64_t q = (uint64_t)q0 + (uint64_t)tid * (uint64_t)a.W;
-                if (q < a.npairs) {
-                    double t = s_dot[tid * R];
-#pragma unroll
-                    for (int r = 1; r < R; r++) t += s_dot[tid * R + r];
-                    __hip_atomic_store(a.part_gemv + q, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-
-        // ---- vector step on the first vec_blocks workers (update_xr_kernel's mapping and arithmetic)
-        if (w < a.vec_blocks) {
-            // what does not depend on p.Ap is fetched BEFORE waiting for it (r, p and x of the thread's first element --
-            // its only one up to N = 65536): the loads' latency then hides under the end of the GEMV phase
-            const uint64_t stride = (uint64_t)a.vec_blocks * kBlock;
-            const uint64_t i_first = (uint64_t)w * kBlock + tid;
-            TV r_first = (TV)0, p_first = (TV)0, x_first = (TV)0;
-            if (i_first < n) {
-                r_first = ld_agent(a.r + i_first);
-                p_first = direct ? pold[i_first] : ld_agent(pold + i_first);
-                x_first = a.x[i_first];
-            }
-            const double pAp = persist_wait(a.bc_pap + w, seq, a.host_err, s_red);
-            const double alpha_d = rr_old / pAp;
-            const TV alpha = (TV)alpha_d;
-            double accv = 0.0;
-            for (uint64_t i = i_first; i < n; i += stride) {
-                const bool first = i == i_first;
-                const TV ri0 = first ? r_first : ld_agent(a.r + i);
-                TV pi;
-                if (direct) pi = first ? p_first : pold[i];
-                else {
-                    pi = ri0 + beta * (first ? p_first : ld_agent(pold + i));
-                    st_agent(pdst + i, pi);
-                }
-                a.x[i] = alpha * pi + (first ? x_first : a.x[i]);
-                const TV ri = -alpha * ld_agent(a.Ap + i) + ri0;
-                st_agent(a.r + i, ri);
-                accv += (double)ri * (double)ri;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // r and p stores have left before the partial says so
-            const double t = block_sum(accv, s_red);
-            if (tid == 0) {
-                if (w == 0) { a.sc->pAp = pAp; a.sc->alpha = alpha_d; }
-                __hip_atomic_store(a.part_vec + w, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (!direct) cur ^= 1;                         // pdst now holds the explicit p_{k-1}
-
-        // ---- hand-over 2: r.r of this iteration, for everybody
-        const double rr_new = persist_wait(a.bc_rr + w, seq, a.host_err, s_red);
-        const CgDecision<TV> d = cg_decide<TV>(a.sc, k, rr_old, bb, rr_new, a.rel_error, a.host_flags, w == 0);
-        if (d.stop) return;                            // like the two-launch form: p is not updated by the stopping iteration
-        if (!(rr_new == rr_new)) return;               // a bounded wait expired somewhere (NaN total): the launch drains
-        beta = d.beta;
-        rr_old = rr_new;
-    }
-    // ---- leave the explicit p of the two-launch form behind: p_k = r_k + beta_k p_{k-1}
-    if (w < a.vec_blocks) {
-        const TV *pold = a.pbuf[cur];
-        const uint64_t stride = (uint64_t)a.vec_blocks * kBlock;
-        for (uint64_t i = (uint64_t)w * kBlock + tid; i < n; i += stride)
-            a.pbuf[0][i] = ld_agent(a.r + i) + beta * ld_agent(pold + i);
-    }
-}
-#endif  // LAM_TUNING_VARIANTS (persistent launch)
 
 // standalone BLAS-1 pieces (lam_hip_dot / lam_hip_axpby and the residual check)
 template <typename TV>

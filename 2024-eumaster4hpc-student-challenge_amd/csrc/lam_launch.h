@@ -24,34 +24,36 @@ template <typename TA, typename TV>
 struct Impl {
     static constexpr int VEC = MatVec<TA>::N;
 
-    // GEMV shapes.  Variants 0-8: gemv_tile_kernel {rows per wave, p-tile columns, p in LDS, rotated
-    // tile order}; 9-18: gemv_coop_kernel {rows per workgroup, tile, waves}; 19-22: the MFMA experiment (bf16).
-    // The PRODUCT library holds the shapes that are some dtype's default: 13 (cooperative rows, 2 rows per EIGHT-wave
+    // GEMV shapes (option "gemv_variant"; the numbers are those of the recorded measurements).  The PRODUCT library holds the
+    // shapes that are some dtype's default: 13 (gemv_coop_kernel, 2 rows per EIGHT-wave
     // workgroup: fp64 production since round 4 -- half as many concurrent row streams as the 4-wave shape, each read 8 KiB at a
     // time: equal at N=65536, 0.4-2.3 % faster at every other size from 8192 to 131072, profiles/r04_variant_vs_size.txt),
-    // 10 (the same with 4 waves: fp32 production, where the two are level), 0 (4 rows per wave: bf16 production) and 17 (4 rows
-    // per 8-wave workgroup: an OPTION, 0.5-0.8 % faster than 13 at exactly 16 column tiles -- N=65536, and its row shards -- and
-    // slower almost everywhere else; not selected by size).  Everything else -- the other tile / cooperative shapes, the grouped probe and the
-    // MFMA-fed bf16 GEMV of BASELINE configs[3]'s comparison (slower than the VALU kernel) -- exists only in the library
+    // 10 (the same with 4 waves: fp32 production, where the two are level), 0 (gemv_tile_kernel, 4 rows per wave: bf16 production)
+    // and 17 (4 rows per 8-wave workgroup: an OPTION, 0.5-0.8 % faster than 13 at exactly 16 column tiles -- N=65536, and its row
+    // shards -- and slower almost everywhere else; not selected by size).  20 and 21 -- the MFMA-fed bf16
+    // GEMV of BASELINE configs[3]'s comparison (slower than the VALU kernel), bf16 storage only -- exist only in the library
     // built with -DLAM_TUNING_VARIANTS (`make tuning` -> liblam_hip_tuning.so; tools/gemv_probe.py, bench.py's MFMA child).
-    static constexpr int kNumVariants = 28;      // 23, 24: tuning probes gemv_coop_group_kernel (2 / 4 row pairs per workgroup);
-                                                 // 25-27: cooperative rows with 8192-column tiles and 4 / 8 rows (bf16 probes, round 4)
+    // Every other number is refused (the shapes that lost: include/lam_hip_tuning.md, "Removed").
     static bool variant_available(int v)
     {
+        switch (v) {
+        case 0: case 10: case 13: case 17: return true;
 #ifdef LAM_TUNING_VARIANTS
-        return v >= 0 && v < kNumVariants;
-#else
-        return v == 0 || v == 10 || v == 13 || v == 17;
+        case 20: case 21: return sizeof(TA) == 2;
 #endif
+        default: return false;
+        }
     }
-    // rows per WORKGROUP of each variant (variants 9.. are the cooperative-row shape: R rows per workgroup)
+    // rows per WORKGROUP of an available variant
     static int variant_rows_per_block(int v)
     {
-        static const int rows[kNumVariants] = {16, 8, 32, 16, 16, 8, 16, 16, 4, 1, 2, 4, 8, 2, 2, 2, 2, 4, 3,
-                                                  /* 19-22: MFMA bf16 experiment (bf16 storage only) */ 8, 8, 16, 4,
-                                                  /* 23, 24: grouped cooperative rows (tuning probe) */ 4, 8,
-                                                  /* 25-27: coop R4 T8192 W4, R4 T8192 W8, R8 T8192 W8 */ 4, 4, 8};
-        return rows[v];
+        switch (v) {
+        case 0: return 16;            // 4 rows per wave
+        case 17: return 4;
+        case 20: return 8;            // MFMA: 2 rows per wave
+        case 21: return 16;           //       4 rows per wave
+        default: return 2;            // 10, 13
+        }
     }
 
     // rows are padded to a multiple of 16 bytes at least (lam_hip_ctx::lda), so the vector kernels serve any N; the any-alignment
@@ -75,27 +77,11 @@ struct Impl {
         if (!fast_ok(c)) { snprintf(buf, sizeof buf, "gemv_generic_kernel<%s,%s>", ta, tv); return buf; }
         const int v = variant(c);
         const char *nt = c->opt_nt ? "true" : "false";
-        struct Tile { int r, tile; bool lds, rot; };
-        static const Tile tiles[9] = {{4, 4096, true, true}, {2, 4096, true, true}, {8, 4096, true, true}, {4, 2048, true, true},
-                                      {4, 8192, true, true}, {2, 8192, true, true}, {4, 4096, false, true}, {4, 4096, true, false},
-                                      {1, 4096, true, true}};
-        struct Coop { int r, tile, waves, unroll; };
-        static const Coop coops[10] = {{1, 4096, 4, 4}, {2, 4096, 4, 4}, {4, 4096, 4, 4}, {8, 4096, 4, 4}, {2, 4096, 8, 4},
-                                       {2, 2048, 4, 4}, {2, 8192, 8, 8}, {2, 8192, 4, 8}, {4, 4096, 8, 4}, {3, 4096, 4, 4}};
-        if (v <= 8)
-            snprintf(buf, sizeof buf, "gemv_tile_kernel<%s,%s,R=%d,TILE=%d,NT=%s,UNROLL=4,LDS=%s,ROT=%s>", ta, tv, tiles[v].r,
-                     tiles[v].tile, nt, tiles[v].lds ? "true" : "false", tiles[v].rot ? "true" : "false");
-        else if (v <= 18)
-            snprintf(buf, sizeof buf, "gemv_coop_kernel<%s,%s,R=%d,TILE=%d,NT=%s,UNROLL=%d,WAVES=%d>", ta, tv, coops[v - 9].r,
-                     coops[v - 9].tile, nt, coops[v - 9].unroll, coops[v - 9].waves);
-        else if (v >= 25)
-            snprintf(buf, sizeof buf, "gemv_coop_kernel<%s,%s,R=%d,TILE=8192,NT=%s,UNROLL=4,WAVES=%d>", ta, tv, v == 27 ? 8 : 4, nt, v == 25 ? 4 : 8);
-        else if (v >= 23)
-            snprintf(buf, sizeof buf, "gemv_coop_group_kernel<%s,%s,GROUP=%d>", ta, tv, v == 23 ? 2 : 4);
-        else {
-            static const int mf[4][2] = {{2, 3}, {2, 1}, {4, 3}, {1, 3}};      // {R, SPLIT} of variants 19..22
-            snprintf(buf, sizeof buf, "gemv_mfma_bf16_kernel<R=%d,TILE=4096,NT=true,SPLIT=%d>", mf[v - 19][0], mf[v - 19][1]);
-        }
+        if (v == 0) snprintf(buf, sizeof buf, "gemv_tile_kernel<%s,%s,R=4,TILE=4096,NT=%s,UNROLL=4,LDS=true,ROT=true>", ta, tv, nt);
+        else if (v >= 20) snprintf(buf, sizeof buf, "gemv_mfma_bf16_kernel<R=%d,TILE=4096,NT=true,SPLIT=%d>", v == 20 ? 2 : 4, v == 20 ? 1 : 3);
+        else
+            snprintf(buf, sizeof buf, "gemv_coop_kernel<%s,%s,R=%d,TILE=4096,NT=%s,UNROLL=4,WAVES=%d>", ta, tv, variant_rows_per_block(v), nt,
+                     v == 10 ? 4 : 8);
         return buf;
     }
 
@@ -115,13 +101,12 @@ struct Impl {
         return (int)((nrows + rows_per_block - 1) / rows_per_block);
     }
 
-    template <int R, int TILE, bool LDS, bool ROT>
     static void launch_tile(const lam_hip_ctx *c, int grid, hipStream_t st, const GemvArgs<TA, TV> &a)
     {
         if (c->opt_nt)
-            hipLaunchKernelGGL((gemv_tile_kernel<TA, TV, R, TILE, true, 4, LDS, ROT>), dim3(grid), dim3(kBlock), 0, st, a);
+            hipLaunchKernelGGL((gemv_tile_kernel<TA, TV, true>), dim3(grid), dim3(kBlock), 0, st, a);
         else
-            hipLaunchKernelGGL((gemv_tile_kernel<TA, TV, R, TILE, false, 4, LDS, ROT>), dim3(grid), dim3(kBlock), 0, st, a);
+            hipLaunchKernelGGL((gemv_tile_kernel<TA, TV, false>), dim3(grid), dim3(kBlock), 0, st, a);
     }
 
     // y = A p reading every pair {i, j} once (lam_kernels.h, "Symmetric product").  The task list is built on first use.
@@ -161,13 +146,13 @@ struct Impl {
     }
 
     // panel: 0 = whole GEMV; 1 = only columns [lo,hi); 2 = everything but [lo,hi), accumulated onto y
-    template <int R, int TILE = 4096, int WAVES = 4, int UNROLL = 4>
+    template <int R, int WAVES>
     static void launch_coop(const lam_hip_ctx *c, int grid, hipStream_t st, const GemvArgs<TA, TV> &a)
     {
         if (c->opt_nt)
-            hipLaunchKernelGGL((gemv_coop_kernel<TA, TV, R, TILE, true, UNROLL, WAVES>), dim3(grid), dim3(WAVES * 64), 0, st, a);
+            hipLaunchKernelGGL((gemv_coop_kernel<TA, TV, R, true, WAVES>), dim3(grid), dim3(WAVES * 64), 0, st, a);
         else
-            hipLaunchKernelGGL((gemv_coop_kernel<TA, TV, R, TILE, false, UNROLL, WAVES>), dim3(grid), dim3(WAVES * 64), 0, st, a);
+            hipLaunchKernelGGL((gemv_coop_kernel<TA, TV, R, false, WAVES>), dim3(grid), dim3(WAVES * 64), 0, st, a);
     }
 
     static int launch_gemv(lam_hip_ctx *c, ShardBase &s, const TV *p, TV *y, double *partial, const CgScalars *sc,
@@ -200,40 +185,15 @@ struct Impl {
         if (fast_ok(c)) {
             switch (variant(c)) {
             default:
-            case 0: launch_tile<4, 4096, true, true>(c, grid, s.stream, a); break;
-            case 10: launch_coop<2>(c, grid, s.stream, a); break;
-            case 13: launch_coop<2, 4096, 8>(c, grid, s.stream, a); break;
-            case 17: launch_coop<4, 4096, 8>(c, grid, s.stream, a); break;
+            case 0: launch_tile(c, grid, s.stream, a); break;
+            case 10: launch_coop<2, 4>(c, grid, s.stream, a); break;
+            case 13: launch_coop<2, 8>(c, grid, s.stream, a); break;
+            case 17: launch_coop<4, 8>(c, grid, s.stream, a); break;
 #ifdef LAM_TUNING_VARIANTS
-            case 1: launch_tile<2, 4096, true, true>(c, grid, s.stream, a); break;
-            case 2: launch_tile<8, 4096, true, true>(c, grid, s.stream, a); break;
-            case 3: launch_tile<4, 2048, true, true>(c, grid, s.stream, a); break;
-            case 4: launch_tile<4, 8192, true, true>(c, grid, s.stream, a); break;
-            case 5: launch_tile<2, 8192, true, true>(c, grid, s.stream, a); break;
-            case 6: launch_tile<4, 4096, false, true>(c, grid, s.stream, a); break;
-            case 7: launch_tile<4, 4096, true, false>(c, grid, s.stream, a); break;
-            case 8: launch_tile<1, 4096, true, true>(c, grid, s.stream, a); break;
-            case 9: launch_coop<1>(c, grid, s.stream, a); break;
-            case 11: launch_coop<4>(c, grid, s.stream, a); break;
-            case 12: launch_coop<8>(c, grid, s.stream, a); break;
-            case 14: launch_coop<2, 2048, 4, 4>(c, grid, s.stream, a); break;
-            case 15: launch_coop<2, 8192, 8, 8>(c, grid, s.stream, a); break;
-            case 16: launch_coop<2, 8192, 4, 8>(c, grid, s.stream, a); break;
-            case 18: launch_coop<3>(c, grid, s.stream, a); break;
-            case 23: hipLaunchKernelGGL((gemv_coop_group_kernel<TA, TV, 2>), dim3(grid), dim3(kBlock), 0, s.stream, a); break;
-            case 24: hipLaunchKernelGGL((gemv_coop_group_kernel<TA, TV, 4>), dim3(grid), dim3(kBlock), 0, s.stream, a); break;
-            case 25: launch_coop<4, 8192, 4, 4>(c, grid, s.stream, a); break;
-            case 26: launch_coop<4, 8192, 8, 4>(c, grid, s.stream, a); break;
-            case 27: launch_coop<8, 8192, 8, 4>(c, grid, s.stream, a); break;
-            case 19: case 20: case 21: case 22:
+            case 20: case 21:                          // variant_available: bf16 storage only
                 if constexpr (sizeof(TA) == 2) {
-                    const int v = variant(c);
-                    if (v == 20) hipLaunchKernelGGL((gemv_mfma_bf16_kernel<2, 4096, true, 1>), dim3(grid), dim3(kBlock), 0, s.stream, a);
-                    else if (v == 21) hipLaunchKernelGGL((gemv_mfma_bf16_kernel<4, 4096, true, 3>), dim3(grid), dim3(kBlock), 0, s.stream, a);
-                    else if (v == 19) hipLaunchKernelGGL((gemv_mfma_bf16_kernel<2, 4096, true, 3>), dim3(grid), dim3(kBlock), 0, s.stream, a);
-                    else hipLaunchKernelGGL((gemv_mfma_bf16_kernel<1, 4096, true, 3>), dim3(grid), dim3(kBlock), 0, s.stream, a);
-                } else {
-                    return fail(c, LAM_HIP_EINVAL, "gemv_variant 19-22 (MFMA) exist for LAM_HIP_BF16 only");
+                    if (variant(c) == 20) hipLaunchKernelGGL((gemv_mfma_bf16_kernel<2, 4096, true, 1>), dim3(grid), dim3(kBlock), 0, s.stream, a);
+                    else hipLaunchKernelGGL((gemv_mfma_bf16_kernel<4, 4096, true, 3>), dim3(grid), dim3(kBlock), 0, s.stream, a);
                 }
                 break;
 #endif
@@ -342,17 +302,17 @@ void release_handles(ShardBase &s)
     if (s.stream) { (void)hipStreamSynchronize(s.stream); (void)hipStreamDestroy(s.stream); s.stream = nullptr; }
 }
 
-// a context whose creation failed half-way: give back what it already holds
-void release_hub(lam_hip_ctx *c)
+// the context's join event (gather-Ap exchange, on shard 0's device)
+void release_join(lam_hip_ctx *c)
 {
     if (c->sh.empty() || hipSetDevice(c->sh[0].dev) != hipSuccess) { (void)hipGetLastError(); return; }
-    for (auto &ev : c->ev_join) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
-    if (c->hub_stream) { (void)hipStreamSynchronize(c->hub_stream); (void)hipStreamDestroy(c->hub_stream); c->hub_stream = nullptr; }
+    if (c->ev_join) { (void)hipEventDestroy(c->ev_join); c->ev_join = nullptr; }
 }
 
+// a context whose creation failed half-way: give back what it already holds
 void abandon(lam_hip_ctx *c)
 {
-    release_hub(c);
+    release_join(c);
     for (auto &s : c->sh) { free_shard(s); release_handles(s); }
     if (c->direct_err) { (void)hipHostFree(c->direct_err); c->direct_err = nullptr; }
 }

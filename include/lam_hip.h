@@ -580,9 +580,10 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
 
 /* ---- options --------------------------------------------------------------------------------- */
 /* name/value pairs; unknown names -> LAM_HIP_EINVAL.  Options that change which kernels an iteration uses need a new
- * lam_hip_cg_init.  Everything here is the PRODUCT; the experiments that were built, measured and lost (persistent launch,
- * enqueue threads, hub join, separate reduction launches, MFMA-fed GEMV, 19 GEMV tuning shapes) exist only in
- * liblam_hip_tuning.so and are described in include/lam_hip_tuning.md -- this library refuses to switch them on.
+ * lam_hip_cg_init.  Everything here is the PRODUCT.  Two experiments that were built, measured and lost are kept in
+ * liblam_hip_tuning.so only (separate reduction launches, "finalize" = 0; the MFMA-fed bf16 GEMV, "gemv_variant" 20 / 21) and are
+ * described in include/lam_hip_tuning.md -- this library refuses to switch them on.  The others (persistent launch, enqueue
+ * threads, hub join, 22 GEMV shapes) were removed from both; that file lists them.
  *
  *   "exchange"      how row shards exchange per iteration.  Default 1 in both multi-GPU topologies (rank mode: 0 until round
  *                   4); environment LAM_HIP_EXCHANGE sets the default of new contexts.
@@ -627,7 +628,8 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *   "gemv_timing"   T (default 8): HIP-event pairs bracket the GEMV -- and the exchange step(s) -- of every T-th iteration
  *                   (lam_hip_stats.t_gemv / t_exchange); 0 = never.
  *   "gemv_variant"  -1 (default) = production shape of the dtype (13 fp64, 10 fp32, 0 bf16); 17 = 4 rows per 8-wave
- *                   workgroup (faster at exactly 16 column tiles only).  Others: tuning build.
+ *                   workgroup (faster at exactly 16 column tiles only); 0, 10 and 13 may be named as well.  20 / 21 (MFMA-fed,
+ *                   bf16 storage): tuning build.  Any other number: LAM_HIP_EINVAL.
  *   "nt_loads" 1, "force_generic" 0, "probe_rows", "panel_lo"/"panel_hi"   kernel-level switches for tests and probes.
  *   "reuse_matrix"  1 (default) = lam_hip_set_problem keeps the matrix allocation when it is large enough (grow-only).
  *   "upload_staging" 1 = lam_hip_upload_rows copies through two pinned staging buffers (default 0: measured slower).

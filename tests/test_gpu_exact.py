@@ -170,24 +170,6 @@ def test_first_step_rank_mode(lam, mock_async, tmp_path, dtype_name, P, exchange
     assert abs(out["rel_err"] - re_host) <= bound, (out["rel_err"], re_host, bound)
 
 
-def _tuning(lam, *args):
-    from test_gpu_parity import _tuning_case
-    _tuning_case(lam, *args)
-
-
-@pytest.mark.parametrize("dtype_name", DTYPES)
-def test_tuning_shapes_known_answer(lam, dtype_name):
-    """The tile and cooperative shapes of the tuning build (tests/tuning_cases.py `exact_gemv`) at two multi-tile sizes."""
-    _tuning(lam, "exact_gemv", dtype_name, 8193)
-    _tuning(lam, "exact_gemv", dtype_name, 12295)
-
-
-@pytest.mark.parametrize("dtype_name", ["F64", "F32"])
-def test_persistent_launch_first_step(lam, dtype_name):
-    """The whole-iteration persistent launch (tuning build, fp64 / fp32 only) takes the same exact first step."""
-    _tuning(lam, "exact_first_step", dtype_name, 12292)      # the persistent launch needs an even n, a multiple of VEC
-
-
 # ------------------------------------------------------------------------------------------------
 # 4. non-finite entries propagate like the reference loop
 # ------------------------------------------------------------------------------------------------

@@ -34,8 +34,8 @@ def _rand_matrix(n, m, seed):
 
 
 def _tuning_case(lam, name, *args, timeout=600):
-    """Run one case of tests/tuning_cases.py in a child process on the TUNING build of the library (the experiments that did
-    not win -- MFMA-fed GEMV, separate reduction launches, enqueue threads, hub, persistent launch -- are not in the product)."""
+    """Run one case of tests/tuning_cases.py in a child process on the TUNING build of the library (the MFMA-fed GEMV and the
+    separate reduction launches are not in the product)."""
     import subprocess
     import sys
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuning_cases.py")
@@ -548,7 +548,7 @@ def test_cg_with_split_gemv_matches_unsplit(lam, oracle, n, lo, hi, generic):
 
 
 # ------------------------------------------------------------------------------------------------
-# MFMA experiment kernels for bf16 storage (gemv_variant 19-22): same answers as the VALU kernel
+# MFMA experiment kernels for bf16 storage (gemv_variant 20, 21): same answers as the VALU kernel
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", [21, 20])
 @pytest.mark.parametrize("n", [512, 4096, 4104, 9000])
@@ -1122,7 +1122,7 @@ def test_launch_chain_variants_are_bit_identical(lam, dtype_name, n, shards):
 
 
 # ------------------------------------------------------------------------------------------------
-# round 3: residency guard of the fused launch, per-shard enqueue threads, event-free iteration loop
+# round 3: residency guard of the fused launch, event-free iteration loop
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype_name,n", [("F64", 4096), ("F32", 2048), ("F64", 1000)])
 def test_fused_update_needs_a_fully_resident_grid(lam, dtype_name, n):
@@ -1159,14 +1159,6 @@ def test_fused_full_update_needs_a_fully_resident_grid(lam, shards, n):
             assert s.get_option("exchange_effective") == 1
             res.append((s.get_option("fuse_effective"), s.stats["num_iters"], s.stats["rel_err"], s.solution().tobytes()))
     assert res[0][0] == 1 and res[1][0] == 0 and res[0][1:] == res[1][1:]
-
-
-@pytest.mark.parametrize("shards,n", [(2, 1024), (3, 3000), (8, 4096), (5, 1001)])
-def test_host_enqueue_variants_are_bit_identical(lam, shards, n):
-    """The three-join event exchange ordered by all-to-all stream waits (product), through a hub stream, and with one enqueue
-    thread per shard (tuning-build experiments: neither reached the host cost of the gather-Ap exchange): same bits --
-    tests/tuning_cases.py `host_enqueue`."""
-    _tuning_case(lam, "host_enqueue", shards, n)
 
 
 @pytest.mark.parametrize("shards,n,dtype_name", [(2, 1024, "F64"), (4, 4096, "F64"), (8, 8192, "F64"), (3, 3000, "F64"), (8, 4104, "F64"),
@@ -1346,27 +1338,28 @@ def test_changing_the_product_kernel_needs_a_new_cg_init(lam):
 
 
 def test_tuning_build_variants(lam):
-    """The GEMV shapes that are nobody's default live in the tuning build only (liblam_hip_tuning.so, `make tuning`):
-    the product library refuses them, and the tuning build computes the same products with every one of them
-    (tools/gemv_probe.py --check, its own process because it loads the other library)."""
+    """The GEMV shapes are 0, 10, 13 and 17; the tuning build (liblam_hip_tuning.so, `make tuning`) adds the MFMA-fed 20 and 21 for
+    bf16 storage and finalize = 0.  The shapes and options that lost were removed: both builds refuse their numbers and names like any
+    unknown one (tests/refused_options.py; the tuning build in one child process, tests/tuning_cases.py `refusals`).  Every shape a
+    build holds computes the same products (tools/gemv_probe.py --check, its own process because it loads the other library)."""
     import subprocess
     import sys
-    with lam.Solver(lam.F64) as s:
+    import refused_options as R
+    with lam.Solver(lam.F64) as s, lam.Solver(lam.BF16) as sb:
         assert s.get_option("tuning_variants") == 0
-        for v in (1, 9, 12, 18, 19, 20, 21, 22, 23):
-            with pytest.raises(lam.LamHipError):
-                s.set_option("gemv_variant", v)
-        for v in (-1, 0, 10, 13, 17):                  # the dtypes' production shapes + the 4-rows-per-8-waves option
-            s.set_option("gemv_variant", v)
-        # ... and the other experiments that did not win: not in the product library either
-        for opt, val in (("persistent", 1), ("persist_chunk", 8), ("host_threads", 1), ("exchange_hub", 1), ("finalize", 0)):
-            with pytest.raises(lam.LamHipError, match="tuning build"):
-                s.set_option(opt, val)
-        for opt, val in (("persistent", 0), ("host_threads", 0), ("exchange_hub", 0), ("finalize", 1)):
-            s.set_option(opt, val)                     # switching them OFF is always accepted
+        for ctx in (s, sb):
+            R.check_removed(lam, ctx)
+            for v in R.MFMA_VARIANTS:
+                assert R.refused(lam, ctx.set_option, "gemv_variant", v), v
+            for v in R.KEPT_VARIANTS:
+                ctx.set_option("gemv_variant", v)
+        with pytest.raises(lam.LamHipError, match="tuning build"):
+            s.set_option("finalize", 0)
+        s.set_option("finalize", 1)
+    _tuning_case(lam, "refusals")
     probe = os.path.join(os.path.dirname(GOLDEN), "..", "tools", "gemv_probe.py")
-    for dtype, variants in (("f64", "0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,23,24,25"), ("f32", "0,8,9,10,12,15,18,23,26"),
-                            ("bf16", "0,1,10,19,20,21,22,25,26,27")):
+    # 4104 = one full 4096-column tile + a ragged 8 columns, 8192 = two tiles
+    for dtype, variants in (("f64", "0,10,13,17"), ("f32", "0,10,13,17"), ("bf16", "0,10,13,17,20,21")):
         r = subprocess.run([sys.executable, probe, "4104", "8192", "--check", "--dtype", dtype, "--variants", variants],
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "FAIL" not in r.stdout and r.stdout.count(" ok") == 2 * len(variants.split(",")), r.stdout + r.stderr[-2000:]
@@ -1462,19 +1455,12 @@ def test_soak_in_kernel_handovers_stay_deterministic(lam, n, cycles, shards):
         assert h.hexdigest() == ref, (rep, fuse, timing)
 
 
-@pytest.mark.parametrize("dtype_name,n", [("F64", 4096), ("F64", 10000), ("F64", 1000), ("F32", 8192), ("F64", 12290)])
-def test_persistent_launch_is_bit_identical_to_the_two_launch_chain(lam, dtype_name, n):
-    """The whole-iteration persistent launch (tuning-build experiment, measured 0.7-2 % slower than the two-launch chain) is
-    the same arithmetic as the product path: identical bits -- tests/tuning_cases.py `persistent`."""
-    _tuning_case(lam, "persistent", dtype_name, n)
-
-
 @pytest.mark.parametrize("build", ["product", "tuning"])
 def test_fuzz_bit_preserving_options(lam, build):
     """tools/fuzz_options.py: random (dtype, N, shards, exchange, iterations, call pattern) cases, each solved with the default
     options and with a random mix of the options that only change HOW an iteration is launched and enqueued -- product
     library: fused / two-kernel vector step, event sampling, the join of the gather-Ap exchange; tuning build in addition:
-    separate reduction launches, enqueue threads, hub, persistent launch and its chunking.  Every case must give the same bits."""
+    separate reduction launches.  Every case must give the same bits."""
     import subprocess
     import sys
     from conftest import ROOT

@@ -3,7 +3,7 @@
 shards, seed, exchange) the solve with default options against the solve with a random combination of the options
 that only change HOW an iteration is launched and enqueued, and with the solve cut into random cg_iterate chunks.
 Product library: fuse_update, gemv_timing, exchange_join.  Tuning build (LAM_HIP_LIB=.../liblam_hip_tuning.so) adds
-the experiments that live there: finalize, host_threads, exchange_hub, persistent / persist_chunk.
+finalize (0 = separate reduction launches).
     usage: fuzz_options.py [cases] [seed] [many]      many: 9 ... 64 shards per case instead of 1 ... 5"""
 import importlib
 import os
@@ -27,7 +27,7 @@ def run(dt, n, shards, seed, opts, chunks):
         st = None
         for c in chunks:
             st = s.cg_iterate(c, 0.0)
-        eff = {k: s.get_option(k) for k in ("fuse_effective", "persistent_effective", "exchange_effective", "symmetric_effective")}
+        eff = {k: s.get_option(k) for k in ("fuse_effective", "exchange_effective", "symmetric_effective")}
         return s.solution(), st["rel_err"], st["num_iters"], eff, s.true_residual()
 
 
@@ -57,13 +57,7 @@ def main():
         ref = run(dt, n, shards, seed, base, [total])
         opts = dict(base, fuse_update=rng.choice((0, 1)), gemv_timing=rng.choice((0, 1, 3, 8)), exchange_join=rng.choice((0, 1)))
         if TUNING:
-            opts.update({"finalize": rng.choice((1, 1, 0)), "host_threads": rng.choice((0, 1)), "exchange_hub": rng.choice((0, 1)),
-                         "persistent": 0 if base.get("symmetric") else rng.choice((0, 1)), "persist_chunk": rng.choice((1, 2, 7, 32))})
-            if opts["persistent"] and not base.get("symmetric"):
-                # the persistent launch shares the tile body of GEMV shape 10 (fp64's default is 13): same shape on both sides
-                base = dict(base, gemv_variant=10)
-                opts["gemv_variant"] = 10
-                ref = run(dt, n, shards, seed, base, [total])
+            opts["finalize"] = rng.choice((1, 1, 0))
         if direct and shards > 1 and exchange == 0 and not base.get("symmetric"):
             # the in-kernel flag exchange between the local shards, one GEMV launch per shard (the own-slice panel of
             # overlap = 1 adds a row's products in another order): same bits as the event exchange; needs finalize = 1

@@ -1,17 +1,15 @@
 #!/usr/bin/env python3
 """GEMV roofline probe: GB/s of the GEMV kernel variants (lam_hip_gemv_only), interleaved rounds in
-one process (cdna_hip_programming.md rule 24).   usage: gemv_probe.py [N ...] [--variants 0,1,..] [--dtype f64|f32|bf16]"""
+one process (cdna_hip_programming.md rule 24).   usage: gemv_probe.py [N ...] [--variants 0,10,..] [--dtype f64|f32|bf16]
+Variants: 0, 10, 13, 17 (every dtype) and the MFMA-fed 20, 21 (bf16 only)."""
 import argparse, importlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# the tuning shapes live in the tuning build of the library (`make tuning`), not in the product library
+# the MFMA shapes (20, 21) live in the tuning build of the library (`make tuning`), not in the product library
 os.environ.setdefault("LAM_HIP_LIB", os.path.join(ROOT, "2024-eumaster4hpc-student-challenge_amd", "liblam_hip_tuning.so"))
 lam = importlib.import_module("2024-eumaster4hpc-student-challenge_amd")
-NAMES = {0: "R4 T4096 lds rot (default)", 1: "R2 T4096", 2: "R8 T4096", 3: "R4 T2048", 4: "R4 T8192", 5: "R2 T8192",
-         6: "R4 T4096 p-from-L2", 7: "R4 T4096 no-rot", 8: "R1 T4096", 9: "coop R1", 10: "coop R2", 11: "coop R4",
-         12: "coop R8", 13: "coop R2 W8", 14: "coop R2 T2048", 15: "coop R2 W8 T8192 u8", 16: "coop R2 W4 T8192 u8",
-         17: "coop R4 W8", 18: "coop R3", 25: "coop R4 T8192 W4", 26: "coop R4 T8192 W8", 27: "coop R8 T8192 W8", 19: "MFMA bf16 R2 split3", 20: "MFMA bf16 R2 split1 (p->bf16)",
-         21: "MFMA bf16 R4 split3", 22: "MFMA bf16 R1 split3", 23: "coop R2 x2 pairs/WG", 24: "coop R2 x4 pairs/WG"}
+NAMES = {0: "R4 T4096 lds rot (bf16 default)", 10: "coop R2 (f32 default)", 13: "coop R2 W8 (f64 default)", 17: "coop R4 W8",
+         20: "MFMA bf16 R2 split1 (p->bf16)", 21: "MFMA bf16 R4 split3"}
 
 def check(a):
     import numpy as np
@@ -44,7 +42,7 @@ def check(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("sizes", nargs="*", type=int, default=[32768])
-    ap.add_argument("--variants", default="0,1,2,3,4,5,6,7,8")
+    ap.add_argument("--variants", default="0,10,13,17")
     ap.add_argument("--dtype", default="f64")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
@@ -78,7 +76,7 @@ def main():
                 ts = sorted(ts)
                 med, best = ts[len(ts) // 2], ts[0]
                 gb = es * rows * n / 1e9
-                print(f"N={n} rows={rows} {a.dtype} v{v} nt={nt} [{NAMES.get(v,'?'):26s}] median {med*1e3:8.4f} ms {gb/med:7.1f} GB/s "
+                print(f"N={n} rows={rows} {a.dtype} v{v} nt={nt} [{NAMES.get(v,'?'):30s}] median {med*1e3:8.4f} ms {gb/med:7.1f} GB/s "
                       f"({gb/med/80:5.1f}% of 8 TB/s)  best {gb/best:7.1f} GB/s", flush=True)
             if a.cg > 0:
                 for v in variants:

@@ -3,10 +3,10 @@
 
 All P shards sit on device 0 and N is small (default 4096: the whole matrix is 134 MB, ~20 us of GEMV), so the wall
 time per iteration is what the HOST needs to enqueue it -- the number that has to stay well below a shard's GEMV on a
-real 8-GPU node (0.61 ms at N=65536, P=8).  Compares round 2's loop (one thread, every stream waits for every other stream: exchange_hub 0), one enqueue
-thread per shard (host_threads 1, the shape of the reference's OpenMP-thread-per-device loop,
-ConjugateGradient_MultiGPUS_CUDA.cu:337-378) and the hub (exchange_hub 1: the streams meet at one join event per
-exchange), prints the runtime calls per iteration, and checks that all give the same bits.
+real 8-GPU node (0.61 ms at N=65536, P=8).  Compares the three exchanges of the product -- the sliced form (every stream waits
+for every other stream, with and without GEMV timing events), gather-Ap (join through shard 0's stream / all-to-all waits) and the
+in-kernel flag exchange (split / one GEMV launch) --, prints the runtime calls per iteration, and checks that all give the same result.
+(Per-shard enqueue threads and a hub stream were measured here too and removed: profiles/r03_host_enqueue_cost.txt.)
 
     usage: host_enqueue_cost.py [N] [iters] [P ...]
 """
@@ -21,8 +21,6 @@ import numpy as np
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 os.environ.setdefault("LAM_HIP_DIRECT_SAME_DEVICE", "1")      # exchange 2 with all shards on one device (one hardware queue per stream above)
 
-# the experiments this tool measures (host_threads / exchange_hub / persistent / finalize = 0) live in the tuning build of the library
-os.environ.setdefault("LAM_HIP_LIB", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "2024-eumaster4hpc-student-challenge_amd", "liblam_hip_tuning.so"))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lam = importlib.import_module("2024-eumaster4hpc-student-challenge_amd")
 
@@ -45,18 +43,11 @@ def main():
         with lam.Solver(lam.F64, device_ids=[0] * P) as s:
             s.generate_random_spd(n, 11, 1e6)
             s.generate_random_rhs(12)
-            tuning = s.get_option("tuning_variants") == 1       # host_threads / exchange_hub exist in the tuning build only
-            for threads, hub, timing, exchange, overlap in ((0, 0, 1, 0, 1), (0, 0, 0, 0, 1), (1, 0, 0, 0, 1), (0, 1, 0, 0, 1), (1, 1, 0, 0, 1),
-                                                            (0, 0, 0, 1, 1), (0, 0, 0, 1, 0), (0, 0, 0, 2, 1), (0, 0, 0, 2, 0)):
-                if P == 1 and (threads == 1 or hub == 1 or exchange != 0):
-                    continue
-                if (threads or hub) and not tuning:
+            for timing, exchange, overlap in ((1, 0, 1), (0, 0, 1), (0, 1, 1), (0, 1, 0), (0, 2, 1), (0, 2, 0)):
+                if P == 1 and exchange != 0:
                     continue
                 if exchange == 1 and n % P != 0:
                     continue
-                if tuning:
-                    s.set_option("host_threads", threads)
-                    s.set_option("exchange_hub", hub)
                 s.set_option("gemv_timing", timing)
                 s.set_option("exchange", exchange)
                 if exchange == 1:
@@ -82,7 +73,7 @@ def main():
                 # full-length partials: equal to rounding
                 same = bool(np.array_equal(x, ref)) or ((exchange == 1 or (exchange == 2 and overlap == 1)) and np.linalg.norm(x - ref) <= 1e-9 * np.linalg.norm(ref))
                 kind = {0: "", 1: " gather-Ap join-via-shard0" if overlap else " gather-Ap all-to-all", 2: " split" if overlap else " nosplit"}[exchange]
-                print(f"P={P} exchange={s.get_option('exchange_effective')}{kind} host_threads={threads} exchange_hub={hub} gemv_timing={timing}: HOST {host:7.1f} us/iteration to enqueue, wall {best*1e6:7.1f} us/iteration, thread CPU {cpu:7.1f} us/iteration   calls/iteration: "
+                print(f"P={P} exchange={s.get_option('exchange_effective')}{kind} gemv_timing={timing}: HOST {host:7.1f} us/iteration to enqueue, wall {best*1e6:7.1f} us/iteration, thread CPU {cpu:7.1f} us/iteration   calls/iteration: "
                       + " ".join(f"{k}={per[k]:.1f}" for k in CALLS) + f"   same result as first variant: {same}", flush=True)
                 assert same
 
