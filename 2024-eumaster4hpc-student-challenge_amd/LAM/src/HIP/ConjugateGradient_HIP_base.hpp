@@ -463,6 +463,45 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         return true;
     }
 
+    // Deflated CG for the batch (lam_hip_set_deflation*, lam_hip_solve_many_deflated): the residuals of solve_many_deflated stay
+    // orthogonal to the space W, so the eigenvalues W captures no longer count.  set_deflation: W holds m vectors of get_num_cols()
+    // elements, vector i at W + i * cols (m == 0 clears the space); set_deflation_from_eigs: the first m Ritz vectors of the last
+    // eigs, device to device.  The space belongs to the matrix held: a new matrix invalidates it.  batch_failed() as for solve_many;
+    // members of their own for solve_many's reason.
+    bool set_deflation(int m, const FloatingType *W)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_deflation(_ctx, m, W) != 0) return report("set_deflation");
+        _batch_failed = false;
+        return true;
+    }
+    bool set_deflation_from_eigs(int m)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_deflation_eigs(_ctx, m) != 0) return report("set_deflation_eigs");
+        _batch_failed = false;
+        return true;
+    }
+    // solve_many on the space set before, from x = 0; arguments and results as solve_many's.  Kept shifts (set_shifts_many) are
+    // handed on as ever, and the library refuses a non-zero one: the space belongs to A, not to A + s I.
+    bool solve_many_deflated(int nrhs, const FloatingType *B, FloatingType *X, int max_iters, FloatingType rel_error,
+                             int32_t *num_iters = nullptr, int32_t *converged = nullptr, double *rel_err = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        if (!apply_shifts(nrhs, true)) return false;
+        lam_hip_stats st;
+        if (lam_hip_solve_many_deflated(_ctx, max_iters, (double)rel_error, &st, num_iters, converged, rel_err) != 0)
+            return report("solve_many_deflated");
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        _batch_failed = false;
+        return st.converged != 0;
+    }
+
     // rows held by this process (all of them in the single-process classes), like the reference getters
     size_t get_num_rows() const
     {

@@ -19,6 +19,7 @@ ABI_VERSION = 4     # include/lam_hip.h LAM_HIP_ABI_VERSION
 MAX_RHS = 8         # include/lam_hip.h LAM_HIP_MAX_RHS
 MAX_SHIFTS = 64     # include/lam_hip.h LAM_HIP_MAX_SHIFTS
 MAX_LANCZOS = 256   # include/lam_hip.h LAM_HIP_MAX_LANCZOS
+MAX_DEFLATION = 32  # include/lam_hip.h LAM_HIP_MAX_DEFLATION
 EIG_WHICH = {"smallest": 0, "largest": 1, "both": 2}   # include/lam_hip.h LAM_HIP_EIG_*
 PC_NONE, PC_JACOBI = 0, 1   # include/lam_hip.h LAM_HIP_PC_*: preconditioner of Solver.solve_many / solve_all
 _VEC_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
@@ -153,6 +154,12 @@ def lib():
             "lam_hip_project_out": ([vp, u64, i32, vp, vp, C.POINTER(C.c_double)], i32),
             "lam_hip_tridiag_eigen": ([i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "lam_hip_set_deflation": ([vp, i32, vp], i32),
+            "lam_hip_set_deflation_eigs": ([vp, i32], i32),
+            "lam_hip_solve_many_deflated": ([vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_double)], i32),
+            "lam_hip_deflate_many": ([vp, u64, i32, i32, vp, vp, C.POINTER(C.c_double), vp, C.POINTER(C.c_double)], i32),
+            "lam_hip_chol_inverse": ([i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)], i32),
             "lam_hip_check_symmetry": ([vp, C.POINTER(C.c_double)], i32),
             "lam_hip_debug_symv_plan": ([u64, i32, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)], i32),
             "lam_hip_dot": ([vp, vp, vp, u64, C.POINTER(C.c_double)], i32),
@@ -229,6 +236,25 @@ def tridiag_eigen(alpha, beta, vectors=False):
     if rc != 0:
         raise LamHipError(rc, "lam_hip_tridiag_eigen: k outside 1..MAX_LANCZOS or a non-finite entry")
     return (theta[:k], row[:k], S.T.copy()) if vectors else (theta[:k], row[:k])
+
+
+def chol_inverse(G):
+    """The inverse of the symmetric positive definite matrix G (m x m, m <= MAX_DEFLATION) by the fp64 Cholesky routine the deflation
+    setters call (lam_hip_chol_inverse: host only, no GPU).  Only the lower triangle is read.  A refused pivot raises LamHipError
+    whose message names the column (also in .bad_col; -1: m out of range)."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    assert G.ndim == 2 and G.shape[0] == G.shape[1], "G is square"
+    m = G.shape[0]
+    Ginv = np.zeros((max(m, 1), max(m, 1)), np.float64)
+    bad = C.c_int(-1)
+    dp = C.POINTER(C.c_double)
+    rc = lib().lam_hip_chol_inverse(m, G.ctypes.data_as(dp), Ginv.ctypes.data_as(dp), C.byref(bad))
+    if rc != 0:
+        e = LamHipError(rc, f"lam_hip_chol_inverse: m = {m} outside 1..{MAX_DEFLATION}" if bad.value < 0 else
+                        f"lam_hip_chol_inverse: the pivot of column {bad.value} is not finite or not above rounding level")
+        e.bad_col = bad.value
+        raise e
+    return Ginv[:m, :m]
 
 
 def partition(n, num_shards, shard):
@@ -664,6 +690,55 @@ class Solver:
         dp = C.POINTER(C.c_double)
         self._chk(self._L.lam_hip_get_lanczos(self._h, C.byref(ns), a.ctypes.data_as(dp), b.ctypes.data_as(dp)))
         return a[:ns.value].copy(), b[:ns.value].copy()
+
+    # -- deflated CG for the batch (one shard, F64 / F32) -----------------------------------------
+    def set_deflation(self, W):
+        """The deflation space of solve_deflated (lam_hip_set_deflation): W (m, N), any full-rank set of m <= MAX_DEFLATION vectors;
+        None or an empty W clears it.  A batched solution is no longer readable afterwards."""
+        if W is None or np.size(W) == 0:
+            self._chk(self._L.lam_hip_set_deflation(self._h, 0, None))
+            return
+        W = np.ascontiguousarray(W, dtype=self.vec_dtype)
+        if W.ndim == 1:
+            W = W.reshape(1, -1)
+        assert W.ndim == 2 and W.shape[1] == self.n, "W is (m, N)"
+        self._chk(self._L.lam_hip_set_deflation(self._h, W.shape[0], W.ctypes.data_as(C.c_void_p)))
+
+    def set_deflation_from_eigs(self, m):
+        """The first m Ritz vectors of the last eigs as the deflation space, device to device (lam_hip_set_deflation_eigs)."""
+        self._chk(self._L.lam_hip_set_deflation_eigs(self._h, m))
+
+    def solve_deflated(self, max_iters, rel_error):
+        """Deflated CG on the right-hand sides of set_rhs_many, from x = 0 (lam_hip_solve_many_deflated).  Returns and fills what
+        solve_many does; solutions(), true_residuals() and solve_many(x0="continue") follow as usual."""
+        k = getattr(self, "nrhs", 0)
+        ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        st = Stats()
+        self._chk(self._L.lam_hip_solve_many_deflated(self._h, max_iters, rel_error, C.byref(st), ni.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      cv.ctypes.data_as(C.POINTER(C.c_int32)), re.ctypes.data_as(C.POINTER(C.c_double))))
+        self.stats = st.asdict()
+        self.num_iters_many, self.converged_many, self.rel_err_many = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
+        return self.converged_many
+
+    def deflate_many(self, Wd, Wa, M, U):
+        """The deflation operator alone (lam_hip_deflate_many): Wd, Wa (m, n), M (m, m) fp64, U (nrhs, n).  Returns (coeff, U_new)
+        with coeff[i, j] = Wd[i].U[j] and U_new[j] = U[j] - sum_i (M coeff[:, j])[i] Wa[i] in the vector dtype."""
+        Wd = np.ascontiguousarray(Wd, dtype=self.vec_dtype)
+        Wa = np.ascontiguousarray(Wa, dtype=self.vec_dtype)
+        U = np.ascontiguousarray(U, dtype=self.vec_dtype)
+        if Wd.ndim == 1:
+            Wd, Wa = Wd.reshape(1, -1), Wa.reshape(1, -1)
+        if U.ndim == 1:
+            U = U.reshape(1, -1)
+        U = U.copy()
+        m, n = Wd.shape
+        M = np.ascontiguousarray(M, dtype=np.float64).reshape(m, m)
+        assert Wa.shape == (m, n) and U.shape[1] == n, "Wd and Wa are (m, n), U is (nrhs, n)"
+        coeff = np.zeros((max(m, 1), max(U.shape[0], 1)), np.float64)
+        self._chk(self._L.lam_hip_deflate_many(self._h, n, m, U.shape[0], Wd.ctypes.data_as(C.c_void_p), Wa.ctypes.data_as(C.c_void_p),
+                                               M.ctypes.data_as(C.POINTER(C.c_double)), U.ctypes.data_as(C.c_void_p),
+                                               coeff.ctypes.data_as(C.POINTER(C.c_double))))
+        return coeff[:m, :U.shape[0]], U
 
     # -- single operators -----------------------------------------------------------------------
     def project_out(self, V, u):

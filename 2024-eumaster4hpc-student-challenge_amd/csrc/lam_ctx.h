@@ -130,8 +130,21 @@ struct LanczosState {
     std::vector<double> alpha, beta, theta;   // alpha[steps], beta[steps]; theta[nfound] in the order `which` asked for
 };
 
+// lam_hip_set_deflation* (lam_deflate.h): the deflation space W of lam_hip_solve_many_deflated, A W and the inverse of W^T A W, next to
+// the batch's vectors.  2 * m * pitch elements, built aside and swapped in by a successful call only (a refused call leaves the previous
+// space), released with the batch (multi_release).  The space belongs to the matrix content: gen follows lam_hip_ctx::matrix_gen.
+struct DeflateState {
+    void *W = nullptr, *AW = nullptr;    // m rows of `pitch` elements each, zero behind element n of every row
+    double *Ginv = nullptr;      // device, m x m: (W^T A W)^-1, symmetric
+    double *part = nullptr;      // [kVecBlocksMax / 4][kMaxDeflation * kMaxRhs] partials of the dots; kept across spaces
+    int m = 0;                   // 0: no space
+    uint64_t pitch = 0;
+    uint64_t gen = ~0ull;        // matrix_gen the space was built on
+};
+
 struct MultiState {
     LanczosState lz;
+    DeflateState df;
     uint64_t n = 0;             // the problem size the buffers were allocated for (0: none)
     void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out

@@ -50,6 +50,7 @@ using namespace lam;
 #include "lam_iterate.h"
 #include "lam_multi.h"
 #include "lam_eigs.h"
+#include "lam_deflate.h"
 
 
 // =================================================================================================
@@ -1144,6 +1145,7 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "panel_lo")) *value = c->opt_panel_lo;
     else if (!strcmp(name, "panel_hi")) *value = c->opt_panel_hi;
     else if (!strcmp(name, "multi_rhs_k")) *value = c->multi.last_K;
+    else if (!strcmp(name, "deflation_m")) *value = deflate_valid(c) ? c->multi.df.m : 0;
     else return LAM_HIP_EINVAL;
     return 0;
 }

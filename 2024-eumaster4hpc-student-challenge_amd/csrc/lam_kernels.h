@@ -44,6 +44,7 @@
 
 #include "lam_host_plan.h"
 #include "lam_host_tridiag.h"
+#include "lam_host_chol.h"
 
 namespace lam {
 
@@ -3439,6 +3440,216 @@ lanczos_residual_kernel(const TV *__restrict__ Y, const TV *__restrict__ AY, Lan
             partial_yy[(size_t)j * gridDim.x + blockIdx.x] = ty;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Deflated CG for the batch (lam_hip_set_deflation*, lam_hip_solve_many_deflated, lam_hip_deflate_many; host side: lam_deflate.h).
+// The operator u_c -= Wa (M (Wd^T u_c)) on the K interleaved columns of a batched vector, as two launches on lanczos_dots_kernel's and
+// lanczos_apply_kernel's plan:
+//   deflate_dots_kernel    partial[block][i * K + c] of d_ic = Wd_i.u_c, i < m, c < K
+//   deflate_apply_kernel   d from the partials in block order ; mu_c = M d_c (fp64, ascending index) ; u_c = fma(-(TV)mu_ic, Wa_i, u_c),
+//                          i ascending ; START: u_c = the fma chain of +(TV)mu_ic Wa_i from 0 (the deflated start vector x0)
+// The basis rows are the Lanczos basis' (row i at W + i * pitch); the vector is the batch's, element [row * K + c], so the VEC rows of
+// one 16-byte load of a basis row meet K 16-byte loads of the vector.  A workgroup holds its slab of the vector in registers
+// (deflate_hold<K>() 16-byte vectors of rows per thread and round, K times as many of the vector) and streams the basis rows past it.
+// All sums are fp64 and of fixed order; no floating-point atomics; columns never mix: d_c, mu_c and the chain of column c read column c
+// alone, so a NaN stays in its column.  sc (may be null): the batch's scalars -- both launches return on all_stop, and the apply launch
+// leaves a stopped column's elements with the bits it loaded (it runs behind multi_p_kernel in stream order: the flags are final).
+// ---------------------------------------------------------------------------------------------
+constexpr int kDeflateSplit = 16;     // gridDim.y of deflate_dots_kernel, as kLanczosSplit
+template <int K>
+constexpr int deflate_hold() { return K == 1 ? 4 : (K == 2 ? 2 : 1); }
+
+// the VEC * K elements of the K-interleaved x that belong to rows idx .. idx + VEC - 1 (idx a multiple of VEC): K 16-byte loads where
+// the rows all lie in front of `end`, else the elements whose row does, and zeros
+template <typename TV, int K>
+__device__ __forceinline__ void deflate_load(const TV *__restrict__ x, uint64_t idx, uint64_t end, TV (&out)[16 / sizeof(TV) * K])
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    typedef TV vec_t __attribute__((ext_vector_type(VEC)));
+    if (idx + VEC <= end) {
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+            const vec_t v = *reinterpret_cast<const vec_t *>(x + idx * K + q * VEC);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) out[q * VEC + e] = v[e];
+        }
+    } else {
+#pragma unroll
+        for (int f = 0; f < VEC * K; f++) out[f] = idx + f / K < end ? x[idx * K + f] : (TV)0;
+    }
+}
+template <typename TV, int K>
+__device__ __forceinline__ void deflate_store(TV *__restrict__ x, uint64_t idx, uint64_t end, const TV (&in)[16 / sizeof(TV) * K])
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    typedef TV vec_t __attribute__((ext_vector_type(VEC)));
+    if (idx + VEC <= end) {
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+            vec_t v;
+#pragma unroll
+            for (int e = 0; e < VEC; e++) v[e] = in[q * VEC + e];
+            *reinterpret_cast<vec_t *>(x + idx * K + q * VEC) = v;
+        }
+    } else {
+#pragma unroll
+        for (int f = 0; f < VEC * K; f++)
+            if (idx + f / K < end) x[idx * K + f] = in[f];
+    }
+}
+
+// workgroup (x, y): slab x of the rows, basis rows i = y, y + gridDim.y, ... < m; partial[x * m * K + i * K + c]
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+deflate_dots_kernel(const MultiScalars *sc, const TV *__restrict__ W, uint64_t pitch, int m, const TV *__restrict__ U, uint64_t n,
+                    double *__restrict__ partial)
+{
+    constexpr int VEC = 16 / sizeof(TV), HOLD = deflate_hold<K>();
+    __shared__ double s_acc[kMaxDeflation][K][kWaves];
+    if (sc != nullptr && sc->all_stop) return;
+    uint64_t first, end;
+    lanczos_slab<TV>(n, &first, &end);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr uint64_t ROUND = (uint64_t)kBlock * VEC * HOLD;
+    bool round0 = true;
+    for (uint64_t base = first; round0 || base < end; base += ROUND) {
+        TV ur[HOLD][VEC * K];
+#pragma unroll
+        for (int h = 0; h < HOLD; h++) deflate_load<TV, K>(U, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, ur[h]);
+        for (int i = blockIdx.y; i < m; i += gridDim.y) {
+            const TV *wi = W + (uint64_t)i * pitch;
+            double a[K];
+#pragma unroll
+            for (int c = 0; c < K; c++) a[c] = 0.0;
+#pragma unroll
+            for (int h = 0; h < HOLD; h++) {
+                TV vr[VEC];
+                lanczos_load<TV>(wi, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, vr);
+#pragma unroll
+                for (int e = 0; e < VEC; e++)
+#pragma unroll
+                    for (int c = 0; c < K; c++) a[c] = __builtin_fma((double)vr[e], (double)ur[h][e * K + c], a[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < K; c++) {
+                const double t = wave_sum(a[c]);
+                if (lane == 0) s_acc[i][c][wave] = round0 ? t : s_acc[i][c][wave] + t;
+            }
+        }
+        round0 = false;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < m * K; t += kBlock) {
+        const int i = t / K, c = t % K;
+        if (i % (int)gridDim.y != (int)blockIdx.y) continue;
+        double s = s_acc[i][c][0];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) s += s_acc[i][c][w];
+        partial[(size_t)blockIdx.x * m * K + t] = s;
+    }
+}
+
+// M: m x m, row-major, fp64 (Ginv of the space, or the caller's).  coeff (may be null): d_ic in fp64 at coeff[i * ncoeff + c],
+// c < ncoeff, by workgroup 0.  START: U is not read; the rows behind row n are zeroed in this K's layout (see multi_init_kernel).
+template <typename TV, int K, bool START>
+__global__ void __launch_bounds__(kBlock)
+deflate_apply_kernel(const MultiScalars *sc, const double *__restrict__ partial, int nred, const double *__restrict__ M,
+                     const TV *__restrict__ W, uint64_t pitch, int m, TV *__restrict__ U, uint64_t n, double *__restrict__ coeff, int ncoeff)
+{
+    constexpr int VEC = 16 / sizeof(TV), HOLD = deflate_hold<K>();
+    __shared__ double s_d[kMaxDeflation * K];
+    __shared__ TV s_mu[kMaxDeflation * K];
+    if (sc != nullptr && sc->all_stop) return;
+    const int npairs = m * K;
+    for (int t = threadIdx.x; t < npairs; t += kBlock) {
+        double a = 0.0;
+        for (int b = 0; b < nred; b++) a += partial[(size_t)b * npairs + t];
+        s_d[t] = a;
+        if (coeff != nullptr && blockIdx.x == 0 && t % K < ncoeff) coeff[(size_t)(t / K) * ncoeff + t % K] = a;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < npairs; t += kBlock) {
+        const int i = t / K, c = t % K;
+        double mu = 0.0;
+        for (int l = 0; l < m; l++) mu = __builtin_fma(M[(size_t)i * m + l], s_d[l * K + c], mu);
+        s_mu[t] = START ? (TV)mu : -(TV)mu;
+    }
+    __syncthreads();
+    bool run[K];
+#pragma unroll
+    for (int c = 0; c < K; c++) run[c] = sc == nullptr || sc->col[c].stop == 0;
+    if constexpr (START)
+        if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) U[n * K + threadIdx.x] = (TV)0;
+    uint64_t first, end;
+    lanczos_slab<TV>(n, &first, &end);
+    constexpr uint64_t ROUND = (uint64_t)kBlock * VEC * HOLD;
+    for (uint64_t base = first; base < end; base += ROUND) {
+        TV ur[HOLD][VEC * K];
+#pragma unroll
+        for (int h = 0; h < HOLD; h++) {
+            if constexpr (START) {
+#pragma unroll
+                for (int f = 0; f < VEC * K; f++) ur[h][f] = (TV)0;
+            } else {
+                deflate_load<TV, K>(U, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, ur[h]);
+            }
+        }
+#pragma unroll 2
+        for (int i = 0; i < m; i++) {
+            const TV *wi = W + (uint64_t)i * pitch;
+            TV mu[K];
+#pragma unroll
+            for (int c = 0; c < K; c++) mu[c] = s_mu[i * K + c];
+#pragma unroll
+            for (int h = 0; h < HOLD; h++) {
+                TV vr[VEC];
+                lanczos_load<TV>(wi, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, vr);
+#pragma unroll
+                for (int e = 0; e < VEC; e++)
+#pragma unroll
+                    for (int c = 0; c < K; c++)
+                        ur[h][e * K + c] = run[c] ? fma_tv(mu[c], vr[e], ur[h][e * K + c]) : ur[h][e * K + c];
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < HOLD; h++) deflate_store<TV, K>(U, base + ((uint64_t)h * kBlock + threadIdx.x) * VEC, end, ur[h]);
+    }
+}
+
+// G[i * ldg + c] = the nred partials of (i, c) in block order, i < m, c < count: the columns of W^T (A W) one group of the product at
+// a time (lam_hip_set_deflation*); one workgroup
+template <int K>
+__global__ void __launch_bounds__(kBlock)
+deflate_gram_kernel(const double *__restrict__ partial, int nred, int m, int count, double *__restrict__ G, int ldg)
+{
+    const int npairs = m * K;
+    for (int t = threadIdx.x; t < npairs; t += kBlock) {
+        if (t % K >= count) continue;
+        double a = 0.0;
+        for (int b = 0; b < nred; b++) a += partial[(size_t)b * npairs + t];
+        G[(size_t)(t / K) * ldg + t % K] = a;
+    }
+}
+
+// basis rows (row j at rows + j * pitch) <-> the [n][K] interleaved vector of a group of `count` of them, padding columns zero
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+deflate_gather_kernel(const TV *__restrict__ rows, uint64_t pitch, int count, TV *__restrict__ inter, uint64_t n)
+{
+    if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) inter[n * K + threadIdx.x] = (TV)0;      // see multi_init_kernel
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++) inter[i * K + j] = j < count ? rows[(uint64_t)j * pitch + i] : (TV)0;
+}
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+deflate_scatter_kernel(const TV *__restrict__ inter, int count, TV *__restrict__ rows, uint64_t pitch, uint64_t n)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++)
+            if (j < count) rows[(uint64_t)j * pitch + i] = inter[i * K + j];
 }
 
 

@@ -62,6 +62,7 @@ void multi_release(lam_hip_ctx *c)
     free_dev({m.mr.W, m.mr.WOLD, m.mr.sc});
     symv_dev_release(m.sym);
     free_dev({m.lz.V, m.lz.U, m.lz.Y, m.lz.part, m.lz.part_uu, m.lz.S, m.lz.sc});
+    free_dev({m.df.W, m.df.AW, m.df.Ginv, m.df.part});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {
@@ -636,8 +637,13 @@ int multi_solve_checks(lam_hip_ctx *c, const char *fn, int precond, int max_iter
     return 0;
 }
 
-// where a batched solve starts: x = 0, a guess given on the host, or the batch's own last solution
-enum MultiGuess { kGuessNone, kGuessHost, kGuessCurrent };
+// where a batched solve starts: x = 0, a guess given on the host, the batch's own last solution, or the deflated start vector
+// x0 = W (W^T A W)^-1 W^T b built on the device (lam_hip_solve_many_deflated)
+enum MultiGuess { kGuessNone, kGuessHost, kGuessCurrent, kGuessDeflated };
+
+// lam_deflate.h: the two launches of the deflated start vector (into P) and of p -= W Ginv (AW)^T r (counted: inside the iteration)
+template <typename TV, int K> int deflate_start(lam_hip_ctx *c);
+template <typename TV, int K> int deflate_project(lam_hip_ctx *c, bool counted);
 
 // lam_hip_solve_many (precond = LAM_HIP_PC_NONE), lam_hip_solve_many_pc and lam_hip_solve_many_x0: one body, one sequence of
 // launches.  The Jacobi-preconditioned batch runs the PC = true instantiations of the four vector kernels on dinv and a second
@@ -646,6 +652,8 @@ enum MultiGuess { kGuessNone, kGuessHost, kGuessCurrent };
 // A x0 in AP with one more product launch and runs the GUESS = true instantiations of the two init kernels.
 // mshift (lam_hip_solve_mshift only, null for every other entry point): the multi-shift state the K = 1 seed batch drives -- one init
 // launch in front of the loop and one step launch behind every multi_p_kernel; nothing else changes, the seed's progress word decides.
+// guess == kGuessDeflated (lam_hip_solve_many_deflated only): the guess is built in P by deflate_start, and deflate_project's two
+// launches follow the init launches and every multi_p_kernel; the three launches of the plain batch are the ones they were.
 int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, const void *x0_host, int max_iters, double rel_error,
                 lam_hip_stats *st, int32_t *num_iters, int32_t *converged, double *rel_err, MshiftState *mshift = nullptr)
 {
@@ -697,6 +705,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
         auto init = [&]() -> int {
             if (guess == kGuessHost) LAMCHK(multi_upload(c, m.nrhs, m.K, x0_host, m.P));
             if (guess == kGuessCurrent) LAMCHK(multi_stage_solution(c, m.X, m.K));
+            if (guess == kGuessDeflated) LAMCHK((deflate_start<TV, K>(c)));
             // GUESS: AP = A x0 ((A + s_j I) x0 of a shifted batch) of the guess staged in P, outside the iteration's scalars and partials
             if (GUESS) LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr, shift)));
             // x = 0, r = b, p = b, bb_j = b_j.b_j  (PC: p = dinv o b, rz_j = b_j.(dinv o b_j));  GUESS: x = x0, r = b - A x0, p = r,
@@ -714,6 +723,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
                                    (TV *)mshift->XS, (TV *)mshift->PS, c->n, mshift->nshifts, dl, mshift->sc);
                 HIPCHK(c, hipGetLastError());
             }
+            if (guess == kGuessDeflated) LAMCHK((deflate_project<TV, K>(c, false)));
             return 0;
         };
         auto rest = [&](int k) -> int {
@@ -729,6 +739,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
                                    (TV *)mshift->PS, c->n);
                 LAUNCHED(c);
             }
+            if (guess == kGuessDeflated) LAMCHK((deflate_project<TV, K>(c, true)));
             return 0;
         };
         return multi_drive<TA, TV, K>(c, max_iters, (const TV *)m.P, (TV *)m.AP, m.sc, shift, init, rest, &timing);

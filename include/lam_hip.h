@@ -58,7 +58,9 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): option "symmetric_many" and the get-only option "symmetric_many_effective".
  *      With "symmetric_many" at its default 0 every result is what it was.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_LANCZOS, LAM_HIP_EIG_SMALLEST / _LARGEST / _BOTH, lam_hip_eigs,
- *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen. */
+ *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen.
+ *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_DEFLATION, lam_hip_set_deflation, lam_hip_set_deflation_eigs,
+ *      lam_hip_solve_many_deflated, lam_hip_deflate_many, lam_hip_chol_inverse and the get-only option "deflation_m". */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -524,6 +526,74 @@ int lam_hip_eig_residuals(lam_hip_ctx *ctx, int nev, double *res);
  * 1..LAM_HIP_MAX_LANCZOS, a NULL array or a non-finite entry: LAM_HIP_EINVAL. */
 int lam_hip_tridiag_eigen(int k, const double *alpha, const double *beta, double *theta, double *last_row, double *S);
 
+/* ---- deflated CG for the batch ----------------------------------------------------------------
+ * CG whose residuals stay orthogonal to a small subspace W (Nicolaides; Saad, Yeung, Erhel, Guyomarc'h, SISC 2000): it converges as
+ * if the eigenvalues W captures were absent.  W is typically the Ritz vectors lam_hip_eigs left on the device, but any W of full
+ * rank is legal.  No reference counterpart.  One shard, LAM_HIP_F64 / LAM_HIP_F32, as the batch itself.
+ *
+ * lam_hip_set_deflation: W_host holds m vectors of N elements (vector dtype), vector i at W_host + i*N; m == 0 clears the space.
+ * lam_hip_set_deflation_eigs: the first m Ritz vectors of the last lam_hip_eigs, copied device to device.
+ *   - W goes into a device basis pitched and zero-padded like the Lanczos basis; A W comes from the batch's product launch in
+ *     groups of up to 8 columns (up to 4 under option "symmetric_many", whose two-launch product then runs) -- the plain product of
+ *     A, shifts are not applied; G = W^T (A W) from fp64 sums of fixed order; the host symmetrises G, factors it (Cholesky, fp64:
+ *     lam_hip_chol_inverse's routine) and uploads G^-1;
+ *   - it uses the batch's staging vectors: a batched or multi-shift solution is no longer readable afterwards (LAM_HIP_ESTATE),
+ *     exactly as after lam_hip_gemv_many; the right-hand sides, the shifts, the eigen-solution and the single-vector state are
+ *     left alone; "multi_rhs_k" reports the last group's K;
+ *   - refusals: what the batch refuses, with the same codes and words (several shards, rank mode, LAM_HIP_BF16); no matrix:
+ *     LAM_HIP_ESTATE; m outside 0..min(N, LAM_HIP_MAX_DEFLATION): LAM_HIP_EINVAL; a non-finite value in W_host: LAM_HIP_EINVAL
+ *     naming the vector and the element; a pivot of the factorisation that is not finite, or at most N * u * max_i G_ii (u the unit
+ *     roundoff of the vector dtype: the rounding error of G's own entries, lam_hip_eigs' breakdown rule): LAM_HIP_EINVAL naming the
+ *     column -- W is numerically rank-deficient there; _eigs without an eigen-solution: LAM_HIP_ESTATE, with m above its nfound:
+ *     LAM_HIP_EINVAL.  A refused call sets nothing: the previous space stays;
+ *   - lifetime: the space belongs to the matrix content.  lam_hip_set_problem, an upload or a generator call invalidates it
+ *     (lam_hip_solve_many_deflated then returns LAM_HIP_ESTATE, "deflation_m" reads 0); lam_hip_eigs, lam_hip_set_rhs_many and
+ *     every solve leave it alone.  Memory: 2 * m * N elements, built aside and swapped in on success, released with the batch.
+ *
+ * lam_hip_solve_many_deflated solves the right-hand sides of the last lam_hip_set_rhs_many from x = 0, every column on its own,
+ * all scalars fp64 (TV: the vector dtype; Ginv = G^-1):
+ *       c = W^T b ; mu = Ginv c ; x0 = the fma chain over i ascending of (TV)mu_i w_i, from 0
+ *       r = b - A x0 (rounded to TV) ; bb = b.b ; rr = r.r
+ *       k = 0: sqrt(rr/bb) < rel_error -> born stopped (num_iters 0, x = x0)
+ *       d = (AW)^T r ; mu = Ginv d ; p = r ; p = fma(-(TV)mu_i, w_i, p), i ascending
+ *       k = 1..max_iters:  the plain batch's iteration (product ; alpha = rr / p.Ap, x, r ; stop test, p = r + beta p) ;
+ *                          d = (AW)^T r ; mu = Ginv d ; p = fma(-(TV)mu_i, w_i, p)      for the columns still running
+ *   - each mu = Ginv d is an m-term fp64 fma sum in ascending index, rounded to TV once per use; the dots are fp64 sums of fixed
+ *     order; no floating-point atomics: two identical calls give identical bits;
+ *   - the start is lam_hip_solve_many_x0's path with the guess built on the device; an iteration is the plain batch's three
+ *     launches, unchanged, and two more behind them ("hip_calls_launch": 5 per iteration, 6 under "symmetric_many" at K <= 4);
+ *   - a stopped column's p, x and scalars are never changed again; everything else is lam_hip_solve_many_x0's contract: frozen
+ *     columns, NaN and Inf confined to their column, b_j = 0 runs to the cap on 0/0, rel_error <= 0 never stops, max_iters + 1 at
+ *     the cap, max_iters = 0 returns the k = 0 state, zero padding columns, "multi_rhs_k", the stats (gemv_bytes: the product alone);
+ *   - afterwards the batch holds a batched solution: lam_hip_get_solution_many and lam_hip_true_residual_many work on it, and
+ *     lam_hip_solve_many_x0(..., NULL, ...) continues it as plain CG;
+ *   - refusals: the batch's own; no space, or an invalidated one: LAM_HIP_ESTATE; a non-zero shift in force: LAM_HIP_EINVAL naming
+ *     it (A W and G belong to A, not to A + s_j I);
+ *   - out of scope: Jacobi together with deflation; a caller's guess; shifts; MINRES; multi-shift CG; a deflated continuation of an
+ *     earlier solve; refreshing W from the CG run's own Lanczos coefficients (recycling); fusing the apply launch into the p
+ *     update; several shards, rank mode, bf16. */
+#define LAM_HIP_MAX_DEFLATION 32
+int lam_hip_set_deflation(lam_hip_ctx *ctx, int m, const void *W_host);
+int lam_hip_set_deflation_eigs(lam_hip_ctx *ctx, int m);
+int lam_hip_solve_many_deflated(lam_hip_ctx *ctx, int max_iters, double rel_error, lam_hip_stats *stats, int32_t *num_iters,
+                                int32_t *converged, double *rel_err);
+/* The deflation operator alone, with the kernels the solve uses, on host vectors; needs no problem and no matrix, like
+ * lam_hip_project_out (every storage type; LAM_HIP_BF16: float vectors).  Wd_host, Wa_host: m vectors of n elements each (vector
+ * dtype), vector i at + i*n, 1 <= m <= LAM_HIP_MAX_DEFLATION; M: m x m doubles, row-major; U_host: nrhs vectors of n elements,
+ * vector j at U_host + j*n, 1 <= nrhs <= LAM_HIP_MAX_RHS.  coeff[i*nrhs + j] = Wd_i.u_j, an fp64 sum of fixed order (may be NULL);
+ * mu_j = M coeff_j (fp64 fma sum, ascending index); u_j = fma(-(TV)mu_ij, Wa_i, u_j) in ascending i, written back to U_host.
+ * Columns do not mix: a NaN in u_j reaches u_j and coeff[.][j] only. */
+int lam_hip_deflate_many(lam_hip_ctx *ctx, uint64_t n, int m, int nrhs, const void *Wd_host, const void *Wa_host, const double *M,
+                         void *U_host, double *coeff);
+/* Host-only and context-free, like lam_hip_tridiag_eigen: Ginv = G^-1 of the symmetric positive definite m x m matrix G (row-major
+ * doubles; only the lower triangle is read; Ginv may not alias G) by a square-root-free Cholesky factorisation G = L D L^T in fp64,
+ * symmetric bit for bit, and exact where every factor is a power of two.  This
+ * is the routine lam_hip_set_deflation* call (csrc/lam_host_chol.h).  A pivot that is not finite or at most m * 2^-52 * max_i G_ii
+ * (zero to the rounding of the factorisation's own sums: a duplicated column, a NaN): LAM_HIP_EINVAL with *bad_col (may be NULL)
+ * the column; m outside 1..LAM_HIP_MAX_DEFLATION or a NULL matrix: LAM_HIP_EINVAL with *bad_col = -1.  A refused call leaves Ginv
+ * alone. */
+int lam_hip_chol_inverse(int m, const double *G, double *Ginv, int *bad_col);
+
 /* ---- single operators (reference private members / CUDA kernels, for parity tests, roofline
  *      probes and callers that want the BLAS pieces) ------------------------------------------ */
 
@@ -637,7 +707,9 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *                   the context's communicator, 0 without one), "ranks_on_device", "gemv_ns_min_shard" / "gemv_ns_max_shard" (fastest /
  *                   slowest local shard's average GEMV of the last cg_iterate call: their difference is the skew), "host_cpu_ns", "host_enqueue_ns",
  *                   "hip_calls_launch" / "_record" / "_wait" / "_setdevice", "tuning_variants" (1 in the tuning build),
- *                   "multi_rhs_k" (columns of the batched kernels the last lam_hip_*_many call ran: 1, 2, 4 or 8; 0 before). */
+ *                   "multi_rhs_k" (columns of the batched kernels the last lam_hip_*_many call ran: 1, 2, 4 or 8; 0 before),
+ *                   "deflation_m" (vectors of the deflation space in force, lam_hip_set_deflation*; 0 when none is set or a new
+ *                   matrix has invalidated it). */
 int lam_hip_set_option(lam_hip_ctx *ctx, const char *name, int64_t value);
 int lam_hip_get_option(const lam_hip_ctx *ctx, const char *name, int64_t *value);
 
