@@ -502,6 +502,27 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         return st.converged != 0;
     }
 
+    // Block CG for the batch (lam_hip_solve_block): ONE block Krylov space for the nrhs columns, from X = 0; arguments as
+    // solve_many's.  The columns are coupled: num_iters[j] is the first iteration at which column j met the test, converged and
+    // rel_err are the values at exit; breakdown (may be null) receives {iteration (0: none), kind 1 | 2}.  After a breakdown or
+    // the cap the batch holds the last valid iterate, and solve_many_x0(precond, nrhs, nullptr, nullptr, X, ...) continues from it
+    // with the independent recurrences.  Kept shifts are handed on as ever, and the library refuses a non-zero one.
+    bool solve_block(int nrhs, const FloatingType *B, FloatingType *X, int max_iters, FloatingType rel_error, int32_t *num_iters = nullptr,
+                     int32_t *converged = nullptr, double *rel_err = nullptr, int32_t *breakdown = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_set_rhs_many(_ctx, nrhs, B) != 0) return report("set_rhs_many");
+        if (!apply_shifts(nrhs, true)) return false;
+        lam_hip_stats st;
+        if (lam_hip_solve_block(_ctx, max_iters, (double)rel_error, &st, num_iters, converged, rel_err, breakdown) != 0)
+            return report("solve_block");
+        _stats = st;
+        if (X != nullptr && lam_hip_get_solution_many(_ctx, nrhs, X) != 0) return report("get_solution_many");
+        _batch_failed = false;
+        return st.converged != 0;
+    }
+
     // rows held by this process (all of them in the single-process classes), like the reference getters
     size_t get_num_rows() const
     {

@@ -160,6 +160,10 @@ def lib():
                                              C.POINTER(C.c_double)], i32),
             "lam_hip_deflate_many": ([vp, u64, i32, i32, vp, vp, C.POINTER(C.c_double), vp, C.POINTER(C.c_double)], i32),
             "lam_hip_chol_inverse": ([i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)], i32),
+            "lam_hip_solve_block": ([vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_int32)], i32),
+            "lam_hip_block_factor": ([i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(i32)], i32),
             "lam_hip_check_symmetry": ([vp, C.POINTER(C.c_double)], i32),
             "lam_hip_debug_symv_plan": ([u64, i32, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)], i32),
             "lam_hip_dot": ([vp, vp, vp, u64, C.POINTER(C.c_double)], i32),
@@ -255,6 +259,26 @@ def chol_inverse(G):
         e.bad_col = bad.value
         raise e
     return Ginv[:m, :m]
+
+
+def block_factor(G, dtype=F64):
+    """The s x s routines of Solver.solve_block on the symmetric G (s <= MAX_RHS; only the upper triangle is read), under the pivot
+    rule of `dtype` (lam_hip_block_factor: host only, no GPU).  Returns (Ginv, S, Sinv): G^-1 by G = L D L^T, the upper factor of
+    G = S^T S and its inverse.  A failed pivot raises LamHipError whose message names the column (also in .bad_col; -1: s or dtype
+    out of range)."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    assert G.ndim == 2 and G.shape[0] == G.shape[1], "G is square"
+    s = G.shape[0]
+    out = [np.zeros((max(s, 1), max(s, 1)), np.float64) for _ in range(3)]
+    bad = C.c_int(-1)
+    dp = C.POINTER(C.c_double)
+    rc = lib().lam_hip_block_factor(s, dtype, G.ctypes.data_as(dp), *[o.ctypes.data_as(dp) for o in out], C.byref(bad))
+    if rc != 0:
+        e = LamHipError(rc, f"lam_hip_block_factor: s = {s} outside 1..{MAX_RHS} or dtype {dtype} not F64 / F32" if bad.value < 0 else
+                        f"lam_hip_block_factor: the pivot of column {bad.value} is not finite or not above rounding level")
+        e.bad_col = bad.value
+        raise e
+    return tuple(o[:s, :s] for o in out)
 
 
 def partition(n, num_shards, shard):
@@ -739,6 +763,35 @@ class Solver:
                                                M.ctypes.data_as(C.POINTER(C.c_double)), U.ctypes.data_as(C.c_void_p),
                                                coeff.ctypes.data_as(C.POINTER(C.c_double))))
         return coeff[:m, :U.shape[0]], U
+
+    # -- block CG for the batch (one shard, F64 / F32) ---------------------------------------------
+    def solve_block(self, max_iters, rel_error, fallback=False, fallback_max_iters=None):
+        """Block CG on the right-hand sides of set_rhs_many, from X = 0: one block Krylov space for all of them
+        (lam_hip_solve_block).  Returns (num_iters, converged, rel_err, breakdown): per column the first iteration that met the
+        test (max_iters + 1: never) and the values at exit, and breakdown = (iteration, kind), (0, 0) for none; self.stats holds the
+        batch's, self.num_iters_many / converged_many / rel_err_many the per-column arrays.  solutions() and true_residuals()
+        follow as usual.  fallback=True: if some column has not converged (a breakdown, or the cap), solve_many(fallback_max_iters
+        (default: max_iters), rel_error, x0="continue") runs behind it -- the independent recurrences from the block's X -- and
+        converged and rel_err are that solve's; its iteration counts are in self.fallback_iters (None when it did not run)."""
+        k = getattr(self, "nrhs", 0)
+        ni, cv, re = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        bd = np.zeros(2, np.int32)
+        st = Stats()
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._L.lam_hip_solve_block(self._h, max_iters, rel_error, C.byref(st), ni.ctypes.data_as(ip), cv.ctypes.data_as(ip),
+                                              re.ctypes.data_as(C.POINTER(C.c_double)), bd.ctypes.data_as(ip)))
+        self.stats = st.asdict()
+        self.num_iters_many, self.converged_many, self.rel_err_many = ni[:k].copy(), cv[:k].astype(bool), re[:k].copy()
+        self.breakdown = (int(bd[0]), int(bd[1]))
+        self.fallback_iters = None
+        block_iters = self.num_iters_many
+        if fallback and not self.converged_many.all():
+            block_stats = self.stats
+            self.solve_many(max_iters if fallback_max_iters is None else fallback_max_iters, rel_error, x0="continue")
+            self.fallback_iters = self.num_iters_many
+            self.fallback_stats, self.stats = self.stats, block_stats
+            self.num_iters_many = block_iters
+        return block_iters, self.converged_many, self.rel_err_many, self.breakdown
 
     # -- single operators -----------------------------------------------------------------------
     def project_out(self, V, u):

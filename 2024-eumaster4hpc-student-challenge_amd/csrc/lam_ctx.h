@@ -142,9 +142,17 @@ struct DeflateState {
     uint64_t gen = ~0ull;        // matrix_gen the space was built on
 };
 
+// lam_hip_solve_block (lam_block.h): the scalars and the two sets of Gram partials of block CG; its vectors are the batch's own.
+// Allocated by the first call for the batch's n, released with the batch (multi_release).
+struct BlockState {
+    double *part_h = nullptr, *part_g = nullptr;     // [kVecBlocksMax][36]: upper triangles of P^T Z and of Q~^T Q~ per workgroup
+    BlockScalars *sc = nullptr;  // device; the last of the three to be allocated: set means all are
+};
+
 struct MultiState {
     LanczosState lz;
     DeflateState df;
+    BlockState bk;
     uint64_t n = 0;             // the problem size the buffers were allocated for (0: none)
     void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out

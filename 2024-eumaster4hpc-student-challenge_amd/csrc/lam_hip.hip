@@ -51,6 +51,7 @@ using namespace lam;
 #include "lam_multi.h"
 #include "lam_eigs.h"
 #include "lam_deflate.h"
+#include "lam_block.h"
 
 
 // =================================================================================================

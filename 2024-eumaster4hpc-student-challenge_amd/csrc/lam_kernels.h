@@ -45,6 +45,7 @@
 #include "lam_host_plan.h"
 #include "lam_host_tridiag.h"
 #include "lam_host_chol.h"
+#include "lam_host_block.h"
 
 namespace lam {
 
@@ -3650,6 +3651,380 @@ deflate_scatter_kernel(const TV *__restrict__ inter, int count, TV *__restrict__
 #pragma unroll
         for (int j = 0; j < K; j++)
             if (j < count) rows[(uint64_t)j * pitch + i] = inter[i * K + j];
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// Block CG for the batch (lam_hip_solve_block; host side: lam_block.h; the s x s matrices: lam_host_block.h; the recurrence,
+// Dubrulle's BCGrQ with a Cholesky QR: include/lam_hip.h).  The s = nrhs live columns of the batch span ONE block Krylov space.
+// Four launches per iteration: the batch's product Z = A P (multi_launch_gemv, untouched) and
+//   block_gram_kernel   per-workgroup fp64 partials of the upper triangle of U^T V (H = P^T Z; the initial B^T B with U = V = B)
+//   block_step_kernel   H from the partials, H = L D L^T, T = H^-1 ; X += P (T Phi) ; Q~ = Q - Z T ; partials of Q~^T Q~
+//   block_dir_kernel    G from the partials ; rel_err_j = sqrt(Phi_j^T G Phi_j / bb_j) and the stop decision ; G = S^T S ;
+//                       Q = Q~ S^-1 ; P = Q + P S^T ; Phi' = S Phi
+// Vectors are the batch's (B, X, R as Q, P, AP as Z), K-interleaved; the padding columns c >= s are zero and never written.  One
+// thread owns one row at a time (grid-stride): its K values of each vector are K * sizeof(TV) contiguous bytes (16-byte loads where
+// a row has them), the s x s coefficient matrices are read from LDS at an address the whole wave shares, and the Gram kernels keep
+// the K (K + 1) / 2 fp64 accumulators of the upper triangle (36 at K = 8) next to the one row -- VGPR and scratch use: DESIGN §17.
+// Every workgroup sums the partials in the one fixed order of block_pair_sums and factors the s x s matrix itself (thread 0, in
+// LDS), so all of them hold the same bits; no floating-point atomics.  The coefficients are rounded to the vector dtype once and
+// every row's sums are fma chains in ascending column index.
+// Scalars: BlockScalars.  Phi is a ring of two by iteration parity (iteration k reads slot (k + 1) & 1, workgroup 0 of
+// block_dir_kernel writes slot k & 1), the other words have workgroup 0 of one launch as their only writer and reader.  all_stop:
+// workgroup 0 may raise it inside the launch that also reads it, so every workgroup reads it ONCE (thread 0, handed on through LDS
+// behind a barrier) and all its waves take the same branch -- the LDS sums of block_pair_sums need all four.  A workgroup that
+// meets the raised flag returns, which is what it decides itself from the same bits; one that does not decides so on its own.  A
+// breakdown raises all_stop too and posts "stopped" to the progress word.
+// ---------------------------------------------------------------------------------------------
+struct BlockScalars : MultiScalars {     // the prefix: what the product reads (all_stop); col[] is not used
+    double phi[2][kMaxRhs * kMaxRhs];     // s x s, leading dimension s: R = Q Phi
+    double bb[kMaxRhs];                   // b_j.b_j
+    double rel_err[kMaxRhs];              // of the last completed iteration
+    int first_hit[kMaxRhs];               // first iteration at which column j met the stop test (0: never)
+    int iters;                            // last completed iteration
+    int bd_iter, bd_kind, bd_col;         // breakdown: iteration (0: none), 1 = H's pivot, 2 = G's pivot, the column of the pivot
+};
+
+template <int K> constexpr int block_pairs() { return K * (K + 1) / 2; }
+
+// the K values of row i of a K-interleaved vector
+template <typename TV, int K>
+__device__ __forceinline__ void block_load_row(const TV *__restrict__ x, uint64_t i, TV (&out)[K])
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    if constexpr (K % VEC == 0) {
+        typedef TV vec_t __attribute__((ext_vector_type(VEC)));
+#pragma unroll
+        for (int q = 0; q < K / VEC; q++) {
+            const vec_t v = *reinterpret_cast<const vec_t *>(x + i * K + q * VEC);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) out[q * VEC + e] = v[e];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; j++) out[j] = x[i * K + j];
+    }
+}
+template <typename TV, int K>
+__device__ __forceinline__ void block_store_row(TV *__restrict__ x, uint64_t i, const TV (&in)[K])
+{
+    constexpr int VEC = 16 / sizeof(TV);
+    if constexpr (K % VEC == 0) {
+        typedef TV vec_t __attribute__((ext_vector_type(VEC)));
+#pragma unroll
+        for (int q = 0; q < K / VEC; q++) {
+            vec_t v;
+#pragma unroll
+            for (int e = 0; e < VEC; e++) v[e] = in[q * VEC + e];
+            *reinterpret_cast<vec_t *>(x + i * K + q * VEC) = v;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; j++) x[i * K + j] = in[j];
+    }
+}
+
+// acc[pair(i, j)] += u_i v_j for i <= j < K, pairs in row-major order of the upper triangle
+template <typename TV, int K>
+__device__ __forceinline__ void block_gram_row(const TV (&u)[K], const TV (&v)[K], double (&acc)[K * (K + 1) / 2])
+{
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < K; i++)
+#pragma unroll
+        for (int j = i; j < K; j++, t++) acc[t] = __builtin_fma((double)u[i], (double)v[j], acc[t]);
+}
+
+// the workgroup's totals of the accumulators, in fixed order, to partial[block * NP + pair]
+template <int K>
+__device__ __forceinline__ void block_gram_flush(const double (&acc)[K * (K + 1) / 2], double (*s_acc)[kWaves], double *__restrict__ partial)
+{
+    constexpr int NP = block_pairs<K>();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int t = 0; t < NP; t++) {
+        const double w = wave_sum(acc[t]);
+        if (lane == 0) s_acc[t][wave] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < NP) {
+        double a = s_acc[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) a += s_acc[threadIdx.x][w];
+        partial[(size_t)blockIdx.x * NP + threadIdx.x] = a;
+    }
+}
+
+// s_full[i * s + j] = s_full[j * s + i] = the nred partials of pair (i, j), i <= j < s: wave w sums the workgroups w, w + 4, ... in
+// ascending order (lane = pair, so a load is one contiguous run), then the four in ascending order.  The same bits in every workgroup.
+template <int K>
+__device__ __forceinline__ void block_pair_sums(const double *__restrict__ partial, int nred, int s, double (*s_acc)[kWaves],
+                                                double *s_full)
+{
+    constexpr int NP = block_pairs<K>();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane < NP) {
+        double a = 0.0;
+#pragma unroll 4
+        for (int b = wave; b < nred; b += kWaves) a += partial[(size_t)b * NP + lane];
+        s_acc[lane][wave] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < NP) {
+        double a = s_acc[threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) a += s_acc[threadIdx.x][w];
+        // pair index -> (i, j) of the K-wide upper triangle
+        int i = 0, t = threadIdx.x;
+        while (t >= K - i) { t -= K - i; i++; }
+        const int j = i + t;
+        if (j < s) s_full[i * s + j] = s_full[j * s + i] = a;
+    }
+    __syncthreads();
+}
+
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+block_gram_kernel(const MultiScalars *sc, const TV *__restrict__ U, const TV *__restrict__ V, uint64_t n, double *__restrict__ partial)
+{
+    constexpr int NP = block_pairs<K>();
+    __shared__ double s_acc[NP][kWaves];
+    __shared__ int s_stop;
+    if (threadIdx.x == 0) s_stop = sc != nullptr && sc->all_stop;
+    __syncthreads();
+    if (s_stop) return;
+    double acc[NP];
+#pragma unroll
+    for (int t = 0; t < NP; t++) acc[t] = 0.0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        TV u[K], v[K];
+        block_load_row<TV, K>(U, i, u);
+        block_load_row<TV, K>(V, i, v);
+        block_gram_row<TV, K>(u, v, acc);
+    }
+    block_gram_flush<K>(acc, s_acc, partial);
+}
+
+// by-value s x s matrix (leading dimension s) of block_init_kernel
+struct BlockMat { double a[kMaxRhs * kMaxRhs]; };
+
+// Q = B C^-1 (fma chain from 0, i ascending, i <= j: C^-1 is upper triangular), P = Q, X = 0 for the s live columns; the padding
+// columns of all three and the rows behind row n of P are zeroed in this K's layout (see multi_init_kernel).  Workgroup 0 sets the
+// scalars: Phi = C, bb, rel_err = 1 (R = B).
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+block_init_kernel(const TV *__restrict__ B, TV *__restrict__ X, TV *__restrict__ Q, TV *__restrict__ P, uint64_t n, int s, BlockMat C,
+                  BlockMat Cinv, BlockMat bb, BlockScalars *sc, volatile int *host_flags)
+{
+    __shared__ TV s_ci[K * K];
+    for (int t = threadIdx.x; t < K * K; t += kBlock) {
+        const int i = t / K, j = t % K;
+        s_ci[t] = i < s && j < s ? (TV)Cinv.a[i * s + j] : (TV)0;
+    }
+    if (blockIdx.x == 0) {
+        for (int t = threadIdx.x; t < kMaxRhs * kMaxRhs; t += kBlock) {
+            sc->phi[0][t] = t < s * s ? C.a[t] : 0.0;
+            sc->phi[1][t] = 0.0;
+        }
+        if (threadIdx.x < kMaxRhs) {
+            const int j = threadIdx.x;
+            sc->bb[j] = j < s ? bb.a[j] : 0.0;
+            sc->rel_err[j] = j < s ? 1.0 : 0.0;
+            sc->first_hit[j] = 0;
+            CgScalars &c = sc->col[j];
+            c.bb = j < s ? bb.a[j] : 0.0; c.rr[0] = c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0; c.stop = 0;
+        }
+        if (threadIdx.x == 0) {
+            sc->all_stop = 0; sc->pad = 0; sc->iters = 0;
+            sc->bd_iter = 0; sc->bd_kind = 0; sc->bd_col = -1;
+            post_progress(host_flags, 0, false);
+        }
+        if (threadIdx.x < kMultiPadRows * K) P[n * K + threadIdx.x] = (TV)0;
+    }
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        TV b[K], q[K], zero[K];
+        block_load_row<TV, K>(B, i, b);
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            TV a = (TV)0;
+            if (j < s) {
+#pragma unroll
+                for (int l = 0; l <= j; l++) a = fma_tv(b[l], s_ci[l * K + j], a);
+            }
+            q[j] = a;
+            zero[j] = (TV)0;
+        }
+        block_store_row<TV, K>(Q, i, q);
+        block_store_row<TV, K>(P, i, q);
+        block_store_row<TV, K>(X, i, zero);
+    }
+}
+
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+block_step_kernel(const double *__restrict__ part_h, int nred, BlockScalars *sc, int k, int s, const TV *__restrict__ P,
+                  const TV *__restrict__ Z, TV *__restrict__ X, TV *__restrict__ Q, uint64_t n, double *__restrict__ part_g,
+                  volatile int *host_flags)
+{
+    constexpr int NP = block_pairs<K>();
+    constexpr bool F32 = sizeof(TV) == 4;
+    __shared__ double s_acc[NP][kWaves];
+    __shared__ double s_h[K * K], s_l[K * K], s_d[K], s_t[K * K];
+    __shared__ TV s_ct[K * K], s_cx[K * K];         // -T and T Phi, K-wide, zero outside s x s
+    __shared__ int s_bad, s_stop;
+    if (threadIdx.x == 0) s_stop = sc->all_stop;       // one read per workgroup: its waves must not part on a flag raised meanwhile
+    __syncthreads();
+    if (s_stop) return;
+    block_pair_sums<K>(part_h, nred, s, s_acc, s_h);
+    if (threadIdx.x == 0) {
+        int bad;
+        block_ldlt_inverse(s, s_h, block_pivot_floor(s, F32, s_h), s_l, s_d, s_t, &bad);
+        s_bad = bad;
+    }
+    __syncthreads();
+    if (s_bad >= 0) {                               // breakdown kind 1: X stays iterate k - 1
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            sc->bd_iter = k; sc->bd_kind = 1; sc->bd_col = s_bad;
+            sc->all_stop = 1;
+            post_progress(host_flags, k, true);
+        }
+        return;
+    }
+    const double *phi = sc->phi[(k + 1) & 1];
+    for (int t = threadIdx.x; t < K * K; t += kBlock) {
+        const int i = t / K, j = t % K;
+        double cx = 0.0, ct = 0.0;
+        if (i < s && j < s) {
+            for (int l = 0; l < s; l++) cx = __builtin_fma(s_t[i * s + l], phi[l * s + j], cx);
+            ct = -s_t[i * s + j];
+        }
+        s_cx[t] = (TV)cx;
+        s_ct[t] = (TV)ct;
+    }
+    __syncthreads();
+    double acc[NP];
+#pragma unroll
+    for (int t = 0; t < NP; t++) acc[t] = 0.0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        TV p[K], z[K], x[K], q[K];
+        block_load_row<TV, K>(P, i, p);
+        block_load_row<TV, K>(Z, i, z);
+        block_load_row<TV, K>(X, i, x);
+        block_load_row<TV, K>(Q, i, q);
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (j >= s) continue;
+            TV xj = x[j], qj = q[j];
+#pragma unroll
+            for (int l = 0; l < K; l++) {
+                if (l >= s) continue;
+                xj = fma_tv(p[l], s_cx[l * K + j], xj);
+                qj = fma_tv(z[l], s_ct[l * K + j], qj);
+            }
+            x[j] = xj;
+            q[j] = qj;
+        }
+        block_store_row<TV, K>(X, i, x);
+        block_store_row<TV, K>(Q, i, q);
+        block_gram_row<TV, K>(q, q, acc);
+    }
+    block_gram_flush<K>(acc, s_acc, part_g);
+}
+
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+block_dir_kernel(const double *__restrict__ part_g, int nred, BlockScalars *sc, int k, int s, double rel_error, TV *__restrict__ Q,
+                 TV *__restrict__ P, uint64_t n, volatile int *host_flags)
+{
+    constexpr int NP = block_pairs<K>();
+    constexpr bool F32 = sizeof(TV) == 4;
+    __shared__ double s_acc[NP][kWaves];
+    __shared__ double s_g[K * K], s_s[K * K], s_si[K * K], s_rel[K];
+    __shared__ TV s_cs[K * K], s_ci[K * K];         // S and S^-1, K-wide, zero outside s x s
+    __shared__ int s_bad, s_stop;
+    if (threadIdx.x == 0) s_stop = sc->all_stop;       // as in block_step_kernel
+    __syncthreads();
+    if (s_stop) return;
+    block_pair_sums<K>(part_g, nred, s, s_acc, s_g);
+    const double *phi = sc->phi[(k + 1) & 1];
+    if (threadIdx.x < s) {
+        // Phi_j^T G Phi_j = ||r_j||^2 (R = Q~ Phi); Phi is upper triangular, so rows 0 .. j of column j
+        const int j = threadIdx.x;
+        double v = 0.0;
+        for (int a = 0; a <= j; a++) {
+            double w = 0.0;
+            for (int b = 0; b <= j; b++) w = __builtin_fma(s_g[a * s + b], phi[b * s + j], w);
+            v = __builtin_fma(phi[a * s + j], w, v);
+        }
+        if (v < 0.0) v = 0.0;                       // rounding of a vanishing residual; a NaN stays one
+        s_rel[j] = sqrt(v / sc->bb[j]);
+    }
+    __syncthreads();
+    bool all = true;
+    for (int j = 0; j < s; j++) all = all && s_rel[j] < rel_error;
+    if (threadIdx.x == 0) {
+        int bad = -1;
+        if (!all) block_upper(s, s_g, block_pivot_floor(s, F32, s_g), s_s, s_si, &bad);
+        s_bad = bad;
+    }
+    __syncthreads();
+    const bool broke = s_bad >= 0;                  // breakdown kind 2: X is iterate k, and valid
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < s) {
+            const int j = threadIdx.x;
+            sc->rel_err[j] = s_rel[j];
+            if (s_rel[j] < rel_error && sc->first_hit[j] == 0) sc->first_hit[j] = k;
+        }
+        if (!all && !broke) {
+            double *out = sc->phi[k & 1];
+            for (int t = threadIdx.x; t < s * s; t += kBlock) {
+                const int i = t / s, j = t % s;
+                double v = 0.0;
+                for (int l = i; l <= j; l++) v = __builtin_fma(s_s[i * s + l], phi[l * s + j], v);
+                out[t] = v;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            sc->iters = k;
+            if (broke) { sc->bd_iter = k; sc->bd_kind = 2; sc->bd_col = s_bad; }
+            if (all || broke) sc->all_stop = 1;
+            post_progress(host_flags, k, all || broke);
+        }
+    }
+    if (all || broke) return;
+    for (int t = threadIdx.x; t < K * K; t += kBlock) {
+        const int i = t / K, j = t % K;
+        const bool in = i < s && j < s;
+        s_cs[t] = in ? (TV)s_s[i * s + j] : (TV)0;
+        s_ci[t] = in ? (TV)s_si[i * s + j] : (TV)0;
+    }
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        TV qt[K], p[K], q[K], pn[K];
+        block_load_row<TV, K>(Q, i, qt);
+        block_load_row<TV, K>(P, i, p);
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            q[j] = qt[j];
+            pn[j] = p[j];
+            if (j >= s) continue;
+            TV a = (TV)0;
+#pragma unroll
+            for (int l = 0; l <= j; l++) a = fma_tv(qt[l], s_ci[l * K + j], a);
+            q[j] = a;
+            // (P S^T)_j = sum_{l >= j} p_l S_jl
+#pragma unroll
+            for (int l = j; l < K; l++) {
+                if (l >= s) continue;
+                a = fma_tv(p[l], s_cs[j * K + l], a);
+            }
+            pn[j] = a;
+        }
+        block_store_row<TV, K>(Q, i, q);
+        block_store_row<TV, K>(P, i, pn);
+    }
 }
 
 

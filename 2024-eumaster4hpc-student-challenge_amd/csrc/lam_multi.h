@@ -1,7 +1,7 @@
 // lam_multi.h -- several right-hand sides on one matrix: the host side of every batched entry point.  nrhs independent recurrences
-// (NOT block CG) advanced together, one pass over the matrix per iteration.  Kernels: lam_kernels.h ("Several right-hand sides",
-// "Batched MINRES", "Multi-shift CG").  Part of the one translation unit csrc/lam_hip.hip (included from there, in order; not a
-// stand-alone header).
+// (NOT block CG: that is lam_block.h, on this file's state and driver) advanced together, one pass over the matrix per iteration.
+// Kernels: lam_kernels.h ("Several right-hand sides", "Batched MINRES", "Multi-shift CG").  Part of the one translation unit
+// csrc/lam_hip.hip (included from there, in order; not a stand-alone header).
 //
 // Map of the file:
 //   state         multi_release / multi_ensure (MultiState), pcg_ensure (PcgState), minres_ensure, mshift_ensure: allocated lazily for
@@ -63,6 +63,7 @@ void multi_release(lam_hip_ctx *c)
     symv_dev_release(m.sym);
     free_dev({m.lz.V, m.lz.U, m.lz.Y, m.lz.part, m.lz.part_uu, m.lz.S, m.lz.sc});
     free_dev({m.df.W, m.df.AW, m.df.Ginv, m.df.part});
+    free_dev({m.bk.part_h, m.bk.part_g, m.bk.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {

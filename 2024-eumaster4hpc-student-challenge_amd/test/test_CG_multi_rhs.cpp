@@ -3,6 +3,7 @@
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m] [-Y 0|1|2]
 //     test_CG_multi_rhs.out -s N -E nev [-W s|l|b] [-i max_steps] [-e tol] [-t f64|f32] [-Y 0|1|2]
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters -D m [-W s|l|b] [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters -B [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
@@ -30,6 +31,11 @@
 // -W s (smallest, the default), l or b, with its own defaults (min(N, 256) steps, tol 1e-10 / 1e-5 for f64 / f32, the start vector of
 // lam_hip_generate_random_rhs(0)); they become the deflation space (lam_hip_set_deflation_eigs) and the generated right-hand sides are
 // solved on it.  The usual CSV line per column; t_cg is the solve's alone.  -D with -J, -S, -M, -m, -w or -E is a usage error.
+// -B: block CG (lam_hip_solve_block) in place of the plain batch: ONE block Krylov space for the nrhs columns.  The constant columns
+// of the plain driver are multiples of one another, which a block refuses (and periodic columns span
+// a block Krylov space of a few dimensions on this matrix), so column j is b_j[i] = 1 + (((i * 8 + j) * 2654435761) mod 2^32 >> 28).  The usual
+// CSV line per column (num_iters: the first iteration at which the column met the test); one line on STDERR gives the iterations
+// run and the breakdown pair.  -B with -J, -S, -M, -m, -D, -w or -E is a usage error.
 // Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
@@ -237,6 +243,43 @@ static int run_deflated(size_t rows, int nrhs, int m, int which, int max_iters, 
     return 0;
 }
 
+// -B: the nrhs columns by block CG
+template <typename T>
+static int run_block(size_t rows, int nrhs, int max_iters, double rel_error, bool true_res, int sym)
+{
+    using clk = std::chrono::high_resolution_clock;
+    LAM::ConjugateGradient_HIP<T> cg(0);
+    cg.set_text_output(false);
+    const auto t0 = clk::now();
+    if (!cg.generate_matrix(rows, rows)) {
+        fprintf(stderr, "Failed to generate matrix\n");
+        return 1;
+    }
+    const double t_load = std::chrono::duration<double>(clk::now() - t0).count();
+    if (!set_symmetric_many(cg.context(), sym)) return 3;
+    std::vector<T> B((size_t)nrhs * rows);
+    for (int j = 0; j < nrhs; j++)
+        for (size_t i = 0; i < rows; i++) B[(size_t)j * rows + i] = (T)(double)(1u + ((uint32_t)((i * 8 + (size_t)j) * 2654435761ull) >> 28));
+    std::vector<int32_t> iters(nrhs), conv(nrhs);
+    std::vector<double> rel(nrhs), tres(nrhs);
+    int32_t bd[2] = {0, 0};
+    const auto t1 = clk::now();
+    cg.solve_block(nrhs, B.data(), nullptr, max_iters, (T)rel_error, iters.data(), conv.data(), rel.data(), bd);
+    if (cg.batch_failed()) return 3;
+    const double t_cg = std::chrono::duration<double>(clk::now() - t1).count();
+    report_symmetric_many(cg.context(), sym);
+    if (true_res && !cg.true_residual_many(nrhs, tres.data())) return 3;
+    const lam_hip_stats &st = cg.stats();
+    fprintf(stderr, "block CG: %d iterations, breakdown = (%d, %d)\n", (int)st.num_iters, (int)bd[0], (int)bd[1]);
+    for (int j = 0; j < nrhs; j++) {
+        std::cout << rows << "," << 1 << "," << 1 << "," << t_load << "," << st.t_comm_init << "," << st.t_gemv << "," << st.t_iter << ","
+                  << iters[j] << "," << rel[j] << "," << t_cg;
+        if (true_res) std::cout << "," << tres[j];
+        std::cout << std::endl;
+    }
+    return 0;
+}
+
 // "s0,s1,...": 1..LAM_HIP_MAX_SHIFTS numbers (main holds a list without -M to LAM_HIP_MAX_RHS), each finite, nothing else; *negative:
 // one of them is < 0, which main accepts under -m only (it decides once every option is parsed)
 static bool parse_shifts(const char *arg, std::vector<double> *out, bool *negative)
@@ -263,6 +306,7 @@ int main(int argc, char **argv)
     int nev = 0, which = LAM_HIP_EIG_SMALLEST;      // nev == 0: no -E
     int defl = 0;                                    // 0: no -D
     bool d_given = false;
+    bool block = false;                              // -B
     bool bad_eigs = false, i_given = false, s_given = false;
     double rel_error = 1e-9;
     const char *precision = "f64";
@@ -272,7 +316,7 @@ int main(int argc, char **argv)
     bool bad_sym = false;
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:E:W:D:h")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:E:W:D:Bh")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
@@ -287,6 +331,7 @@ int main(int argc, char **argv)
         case 'm': minres = true; break;
         case 'E': nev = atoi(optarg); bad_eigs = bad_eigs || nev < 1; break;
         case 'D': defl = atoi(optarg); d_given = true; break;
+        case 'B': block = true; break;
         case 'W':
             if (!strcmp(optarg, "s")) which = LAM_HIP_EIG_SMALLEST;
             else if (!strcmp(optarg, "l")) which = LAM_HIP_EIG_LARGEST;
@@ -302,13 +347,29 @@ int main(int argc, char **argv)
                     "[-Y 0|1|2 (option symmetric_many: the batched product of up to 4 columns reads every pair of the matrix once)] "
                     "[-E nev (Lanczos eigensolver lam_hip_eigs in place of a solve: nev extreme eigenpairs; -W s|l|b smallest / largest / both, "
                     "-i max_steps up to %d, -e tol; not with -J, -w, -S, -M, -m, -k)] "
-                    "[-D m (deflated CG on m = 1..%d Ritz pairs of lam_hip_eigs, -W s|l|b; not with -J, -w, -S, -M, -m, -E)]\n", argv[0],
+                    "[-D m (deflated CG on m = 1..%d Ritz pairs of lam_hip_eigs, -W s|l|b; not with -J, -w, -S, -M, -m, -E)] "
+                    "[-B (block CG lam_hip_solve_block: one block Krylov space for the nrhs columns; not with -J, -w, -S, -M, -m, -D, -E)]\n", argv[0],
                     LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS, LAM_HIP_MAX_LANCZOS, LAM_HIP_MAX_DEFLATION);
             return opt == 'h' ? 0 : 1;
         }
     }
     if (bad_sym) {
         fprintf(stderr, "Usage: -Y takes 0 (the general batched product), 1 (the symmetric one where it pays) or 2 (always, up to 4 columns)\n");
+        return 1;
+    }
+    if (block) {
+        if (jacobi || warm >= 0 || bad_warm || s_given || mshift || minres || d_given || nev != 0 || bad_eigs) {
+            fprintf(stderr, "Usage: -B takes neither -J, -S, -M, -m, -D, -w nor -E: block CG has no preconditioner, no shifts, no deflation "
+                    "space and no guess\n");
+            return 1;
+        }
+        if (rows == 0 || nrhs < 1 || nrhs > LAM_HIP_MAX_RHS || max_iters < 0) {
+            fprintf(stderr, "Usage: %s -s N -k nrhs (1..%d) -i max_iters -B [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]\n", argv[0], LAM_HIP_MAX_RHS);
+            return 1;
+        }
+        if (!strcmp(precision, "f64")) return run_block<double>(rows, nrhs, max_iters, rel_error, true_res, sym);
+        if (!strcmp(precision, "f32")) return run_block<float>(rows, nrhs, max_iters, rel_error, true_res, sym);
+        fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
         return 1;
     }
     if (d_given) {

@@ -60,7 +60,8 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_LANCZOS, LAM_HIP_EIG_SMALLEST / _LARGEST / _BOTH, lam_hip_eigs,
  *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_DEFLATION, lam_hip_set_deflation, lam_hip_set_deflation_eigs,
- *      lam_hip_solve_many_deflated, lam_hip_deflate_many, lam_hip_chol_inverse and the get-only option "deflation_m". */
+ *      lam_hip_solve_many_deflated, lam_hip_deflate_many, lam_hip_chol_inverse and the get-only option "deflation_m".
+ *      Added under version 4 likewise (purely additive): lam_hip_solve_block and lam_hip_block_factor. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -229,9 +230,10 @@ int lam_hip_true_residual(lam_hip_ctx *ctx, double *rel_res);
 /* ---- several right-hand sides on one matrix ----------------------------------------------------
  * nrhs INDEPENDENT CG recurrences advanced together: per iteration ONE product launch reads the matrix once for all of them
  * (every 16-byte piece of a row meets the nrhs values of p while it is in registers), then one launch updates every x_j, r_j and
- * one every p_j.  This is NOT block CG: column j keeps its own alpha_j, beta_j, r_j.r_j, stop decision and iteration count and
- * follows exactly the recurrence of lam_hip_solve (x = 0, r = p = b; stop test sqrt(rr/bb) < rel_error before the p update;
- * num_iters = max_iters + 1 at the cap).  The reference has no counterpart: its drivers are run once per right-hand-side file.
+ * one every p_j.  This is NOT block CG (that is lam_hip_solve_block, below): column j keeps its own alpha_j, beta_j, r_j.r_j, stop
+ * decision and iteration count and follows exactly the recurrence of lam_hip_solve (x = 0, r = p = b; stop test
+ * sqrt(rr/bb) < rel_error before the p update; num_iters = max_iters + 1 at the cap).  The reference has no counterpart: its
+ * drivers are run once per right-hand-side file.
  *   - a column that has met its stop test is FROZEN: its x, r, scalars and iteration count no longer change while the others run on;
  *   - columns never mix: a NaN or an Inf in one column stays there.  A column with b_j = 0 gives 0/0 in the reference's loop; it
  *     never meets the stop test, so the batch then runs to max_iters, exactly as a single solve of that column would;
@@ -593,6 +595,54 @@ int lam_hip_deflate_many(lam_hip_ctx *ctx, uint64_t n, int m, int nrhs, const vo
  * the column; m outside 1..LAM_HIP_MAX_DEFLATION or a NULL matrix: LAM_HIP_EINVAL with *bad_col = -1.  A refused call leaves Ginv
  * alone. */
 int lam_hip_chol_inverse(int m, const double *G, double *Ginv, int *bad_col);
+
+/* ---- block CG for the batch ---------------------------------------------------------------------
+ * One process, ONE shard, LAM_HIP_F64 / LAM_HIP_F32 storage, like every batched entry point.  No reference counterpart.
+ *
+ * lam_hip_solve_block solves the right-hand sides of the last lam_hip_set_rhs_many from X = 0 with ONE block Krylov space for the
+ * s = nrhs columns: Dubrulle's retooled block CG (BCGrQ) with a Cholesky QR.  Every other batched solver advances nrhs independent
+ * recurrences and saves bytes per iteration only; here the s search directions are shared, so the batch converges as if the s - 1
+ * smallest eigenvalues of A were absent, at no set-up and with no lam_hip_eigs run.  Every small matrix is s x s and fp64; TV is the
+ * vector dtype:
+ *     G = B^T B ; bb_j = G_jj ; G = C^T C (C upper) ; Q = B C^-1 ; Phi = C ; P = Q ; X = 0
+ *     k = 1 .. max_iters:
+ *        Z = A P                             the batch's product launch (option "symmetric_many" serves K <= 4)
+ *        H = P^T Z                           the upper triangle, mirrored
+ *        H = L D L^T ; T = H^-1              a pivot failure: breakdown kind 1, X stays iterate k - 1
+ *        X += P (T Phi) ; Q~ = Q - Z T       coefficients rounded to TV once; fma chains in ascending column index
+ *        G = Q~^T Q~
+ *        rel_err_j = sqrt(Phi_j^T G Phi_j / bb_j)        == ||r_j|| / ||b_j||, because R = Q~ Phi
+ *        every live column < rel_error: stop, converged, X is iterate k
+ *        G = S^T S (S upper)                 a pivot failure: breakdown kind 2, X is iterate k and valid
+ *        Q = Q~ S^-1 ; P = Q + P S^T ; Phi = S Phi
+ * The stop test stands in front of the second factorisation: exact convergence (Q~ = 0) reports "converged, rel_err 0", not a
+ * breakdown.  Pivot rule (both factorisations and the initial G): a pivot fails when it is not finite or at most
+ * s * u_TV * max_i G_ii, u_TV = 2^-53 (fp64) or 2^-24 (fp32) -- lam_hip_eigs' breakdown rule.  Four launches per iteration (five
+ * under "symmetric_many" at K <= 4), all sums fp64 and of fixed order: two identical calls give identical bits.
+ *   - The columns are COUPLED.  The batch stops when ALL live columns meet the test, and no column freezes: num_iters[j] is the first
+ *     iteration at which column j met the test (max_iters + 1 if it never did), converged[j] and rel_err[j] are the values at exit
+ *     (of the last completed iteration).  A NaN or Inf in one column reaches all columns.
+ *   - breakdown (may be NULL): breakdown[0] = the iteration of the breakdown (0: none), breakdown[1] = its kind (1 | 2, 0: none).
+ *     A breakdown ends the solve with return code 0; stats->num_iters counts the completed iterations (k - 1 for kind 1).
+ *   - Afterwards the batch holds a batched solution: lam_hip_get_solution_many and lam_hip_true_residual_many serve it, and after a
+ *     breakdown or the cap lam_hip_solve_many_x0(..., NULL, ...) continues from X with the independent recurrences -- the
+ *     documented recovery.
+ *   - rel_error <= 0 never stops early; a run that converges exactly then ends in breakdown kind 2 and says so.
+ *   - max_iters == 0: X = 0, rel_err = 1, num_iters = 1.  max_iters < 0: LAM_HIP_EINVAL, as for the batch.
+ *   - refusals, with the batch's codes: several shards, rank mode, LAM_HIP_BF16: LAM_HIP_EINVAL; no matrix or no right-hand sides:
+ *     LAM_HIP_ESTATE; a non-zero shift in force: LAM_HIP_EINVAL naming it (a block needs one operator); an initial G = B^T B that
+ *     fails the pivot rule -- a zero or duplicated column, nrhs > N: LAM_HIP_EINVAL naming the column, nothing is iterated.
+ *   - stats are the batch's: gemv_bytes and t_gemv are the product's alone.
+ *   - out of scope: Jacobi or deflation inside the block; a caller's guess; shifts; MINRES; dropping converged columns from the
+ *     block (variable block size); several shards. */
+int lam_hip_solve_block(lam_hip_ctx *ctx, int max_iters, double rel_error, lam_hip_stats *stats, int32_t *num_iters,
+                        int32_t *converged, double *rel_err, int32_t *breakdown /* [2]: iteration (0 = none), kind 1|2 */);
+/* Host-only and context-free, like lam_hip_chol_inverse: the s x s routines of lam_hip_solve_block (csrc/lam_host_block.h, the code
+ * its kernels run) on the symmetric G (row-major doubles, s in 1..LAM_HIP_MAX_RHS; only the upper triangle is read), under the
+ * pivot rule of `dtype` (LAM_HIP_F64 | LAM_HIP_F32).  Ginv = G^-1 by G = L D L^T, symmetric bit for bit; S upper triangular with
+ * G = S^T S, and Sinv = S^-1.  Each output may be NULL.  A failed pivot: LAM_HIP_EINVAL with *bad_col (may be NULL) the column and
+ * the outputs unspecified; s or dtype out of range, or G NULL: LAM_HIP_EINVAL with *bad_col = -1. */
+int lam_hip_block_factor(int s, int dtype, const double *G, double *Ginv, double *S, double *Sinv, int *bad_col);
 
 /* ---- single operators (reference private members / CUDA kernels, for parity tests, roofline
  *      probes and callers that want the BLAS pieces) ------------------------------------------ */
