@@ -203,11 +203,34 @@ struct PcgState {
     double badk_value = 0.0;
 };
 
+// Packed fp64 image of the matrix (option "packed", lam_host_pack.h): what gemv_packed_kernel reads in place of A.  One allocation,
+// grow-only, kept for the life of the context (a large hipFree slows whatever runs next); its content follows
+// lam_hip_ctx::matrix_gen, as sym_checked_gen and PcgState::diag_gen do.  A stays where it is: every other path reads it as before.
+// Auto packs once a content has served kPackAfter plain products: the measured break-even, pack time / (plain - packed product time),
+// at N = 65536 (15.7 ms / 0.244 ms = 64.4) rounded up; 68.7 at N = 32768, 134 at N = 40000 (profiles/packed_parent_vs_branch.txt).
+// From kPackMinBytes of matrix on: N = 32768 (8 GiB) runs 1.050 x the plain kernel, 40000 1.024 x, 65536 1.053 x; N = 20000
+// 0.998 x and N = 10000 0.85 x (three tiles of which the last holds 1808 columns, and too few workgroups to hide the decode).
+constexpr int kPackAfter = 65;
+constexpr uint64_t kPackMinBytes = 8ull << 30;
+struct PackState {
+    void *buf = nullptr;
+    size_t cap = 0;
+    uint64_t nrows = 0, ntiles = 0;      // of the image in buf
+    uint64_t ready_gen = ~0ull;          // matrix_gen the image holds
+    uint64_t refused_gen = ~0ull;        // matrix_gen that is not packable (a tile overflowed) or found no memory: not tried again
+    uint64_t count_gen = ~0ull;          // matrix_gen `plain` counts for
+    uint64_t plain = 0;                  // plain products of the eligible shape since the content changed
+    uint64_t exc_total = 0;              // exception-list values a product reads of the whole image (8 bytes each)
+    double pack_s = 0.0;                 // seconds the last pack took (host clock around the pass)
+};
+
 }  // namespace
 
 struct lam_hip_ctx {
     MultiState multi;
     PcgState pcg;
+    PackState pack;
+    int64_t opt_packed = -1;       // fp64 general product on the packed image: -1 auto, 0 never, 1 pack in front of the next product
     int dtype = LAM_HIP_F64;
     int total_shards = 1;          // P
     int rank = 0, nranks = 1;      // rank mode (one local shard == shard `rank`)
@@ -307,6 +330,13 @@ struct lam_hip_ctx {
     }
     bool symv_active() const { return symv_wanted() && !rank_mode && total_shards == 1; }
     bool symv_multi_active() const { return symv_wanted() && exchange1_ok(); }
+    // the packed image serves the fp64 general product of one shard in its default shape; everything else runs as before
+    bool pack_eligible() const
+    {
+        return opt_packed != 0 && dtype == LAM_HIP_F64 && !rank_mode && total_shards == 1 && opt_symmetric == 0 && opt_generic == 0 &&
+               opt_gemv_variant < 0 && n > 0;
+    }
+    bool pack_active() const { return pack_eligible() && pack.buf != nullptr && pack.ready_gen == matrix_gen; }
     // a shard's record in the symmetric product's gather: its full-length contribution, then (8-byte aligned) its part of p.Ap
     uint64_t symv_stride_bytes() const { return (n * esz_v() + 7) / 8 * 8 + 8; }
 

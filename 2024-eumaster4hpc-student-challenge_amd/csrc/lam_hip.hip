@@ -190,6 +190,7 @@ void lam_hip_destroy(lam_hip_ctx *c)
     }
     multi_release(c);
     close_direct(c);
+    if (c->pack.buf && !c->sh.empty() && hipSetDevice(c->sh[0].dev) == hipSuccess) (void)hipFree(c->pack.buf);
     if (c->agree_buf) (void)hipFree(c->agree_buf);
     for (auto &s : c->sh) {
         if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); continue; }
@@ -220,6 +221,7 @@ int lam_hip_set_problem(lam_hip_ctx *c, uint64_t n)
     c->lda = lam_hip_ctx::pitch_for(n, c->esz_a());
     c->problem_gen++;              // peers' mappings of the old p replica are stale from here on
     c->have_problem = c->have_matrix = c->have_rhs = c->cg_ready = false;
+    c->pack.ready_gen = c->pack.refused_gen = c->pack.count_gen = ~0ull;     // the image belongs to one problem; its allocation stays
     const size_t ea = c->esz_a(), ev = c->esz_v();
     for (auto &s : c->sh) {
         // The matrix allocation is grow-only: a context that loads a smaller system after a large one keeps
@@ -613,6 +615,7 @@ int lam_hip_cg_iterate(lam_hip_ctx *c, int iters, double rel_error, lam_hip_stat
                 if (d != 0) break;
                 harvest_times(c, slot, &times);
             }
+            LAMCHK(pack_maybe(c));               // option "packed": in front of the product step, outside its event pair
             const double te = now_s();
             LAMCHK(enqueue_iteration(c, k, rel_error, slot));
             c->enqueue_ns += (uint64_t)((now_s() - te) * 1e9);
@@ -678,7 +681,7 @@ int lam_hip_cg_iterate(lam_hip_ctx *c, int iters, double rel_error, lam_hip_stat
         st->t_gemv = tmax;
         st->t_exchange = times.samples[0] > 0 ? times.xch_ms * 1e-3 / times.samples[0] : 0.0;
         st->t_comm_init = c->t_comm_init;
-        st->gemv_bytes = (double)c->esz_a() * (double)s0.nrows * (double)c->n + (double)c->esz_v() * (double)(c->n + s0.nrows);
+        st->gemv_bytes = gemv_bytes_now(c, s0);     // of the kernel the call ended on (the packed image's when that one runs)
     }
     (void)enq;
     return 0;
@@ -770,6 +773,7 @@ int lam_hip_gemv(lam_hip_ctx *c, const void *x_host, void *y_host)
     if (!c || !x_host || !y_host) return LAM_HIP_EINVAL;
     if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
     LAMCHK(env_symmetric_check(c));     // LAM_HIP_SYMMETRIC: this may be the first product on this matrix (once per matrix)
+    LAMCHK(pack_maybe(c));
     const size_t ev = c->esz_v();
     for (auto &s : c->sh) {
         LAMCHK(set_dev(c, s));
@@ -817,6 +821,7 @@ int lam_hip_gemv_only(lam_hip_ctx *c, int reps, double *sec)
     if (!c || !sec || reps < 1) return LAM_HIP_EINVAL;
     if (!c->have_matrix) return fail(c, LAM_HIP_ESTATE, "matrix not set");
     LAMCHK(env_symmetric_check(c));     // as lam_hip_gemv
+    LAMCHK(pack_maybe(c));
     c->cg_ready = false;
     double worst = 0.0;
     LAMCHK(dispatch(c, [&](auto impl) -> int {
@@ -1089,6 +1094,11 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
                         (long long)value);
         c->opt_symmetric_many = value;
     }
+    else if (!strcmp(name, "packed")) {
+        if (value < -1 || value > 1)
+            return fail(c, LAM_HIP_EINVAL, "packed = %lld: -1 (automatic), 0 (never) or 1 (pack in front of the next product)", (long long)value);
+        c->opt_packed = value;
+    }
     else if (!strcmp(name, "gemv_timing")) c->opt_gemv_timing = value < 0 ? 0 : value;
     else if (!strcmp(name, "verify_direct")) c->opt_verify_direct = value;
     else if (!strcmp(name, "assume_cus")) { c->opt_assume_cus = value; c->cg_ready = false; }
@@ -1140,6 +1150,10 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "hip_calls_setdevice")) *value = (int64_t)c->n_setdev;
     else if (!strcmp(name, "symmetric")) *value = c->opt_symmetric;
     else if (!strcmp(name, "symmetric_many")) *value = c->opt_symmetric_many;
+    else if (!strcmp(name, "packed")) *value = c->opt_packed;
+    else if (!strcmp(name, "packed_effective")) *value = c->pack_active() ? 1 : 0;
+    else if (!strcmp(name, "packed_bytes")) *value = c->pack_active() ? (int64_t)gemv_bytes_now(c, c->sh[0]) : 0;
+    else if (!strcmp(name, "packed_pack_ns")) *value = c->pack_active() ? (int64_t)(c->pack.pack_s * 1e9) : 0;
     else if (!strcmp(name, "symmetric_many_effective")) *value = c->symv_many_effective ? 1 : 0;
     else if (!strcmp(name, "symmetric_effective")) *value = (c->symv_active() || c->symv_multi_active()) ? 1 : 0;
     else if (!strcmp(name, "exchange_effective")) *value = c->cg_direct ? 2 : ((c->exchange1_ok() && !c->exchange2_wanted()) ? 1 : 0);

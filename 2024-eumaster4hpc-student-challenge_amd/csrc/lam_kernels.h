@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "lam_host_plan.h"
+#include "lam_host_pack.h"
 #include "lam_host_tridiag.h"
 #include "lam_host_chol.h"
 #include "lam_host_block.h"
@@ -741,6 +742,275 @@ gemv_coop_kernel(GemvArgs<TA, TV> a)
         double d = 0.0;
         if (row < a.nrows) {
             TV s = s_part[tid][0];
+#pragma unroll
+            for (int w = 1; w < WAVES; w++) s += s_part[tid][w];
+            if (a.accumulate) s += a.y[row];
+            store_y(a, row, s);
+            d = (double)s * (double)a.p[a.row0 + row];
+        }
+        s_dot[tid] = d;
+    }
+    if (a.partial != nullptr) {
+        __syncthreads();
+        double t = 0.0;
+        if (tid == 0) {
+            t = s_dot[0];
+#pragma unroll
+            for (int r = 1; r < R; r++) t += s_dot[r];
+        }
+        publish_partial(t, a.partial, a.fin);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Packed fp64 matrix (option "packed", format: lam_host_pack.h): the same product from 7/8 of the bytes.
+// ---------------------------------------------------------------------------------------------
+struct PackedMat {
+    const unsigned char *data;   // [nrows][ntiles][kPackGroups][kPackGroupBytes]
+    const double *exc;           // [nrows][ntiles][kPackCap]
+    const uint32_t *hdr;         // [nrows][ntiles]
+    uint32_t ntiles;
+};
+typedef unsigned int pack_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned int pack_u2 __attribute__((ext_vector_type(2)));
+
+// One pass over A: workgroup = one row, tile by tile -- exponent histogram in LDS, the window of kPackWindow binades that holds the
+// most elements, the elements in the product kernel's traversal order, the exception list, the header.  info[0] is set when a
+// (row, tile) has more than kPackCap exceptions (not packable), info[1] counts the list values a product reads (the first
+// kPackFirst of every list whatever its length, then the rest of a longer one).  Thread (wave, lane) encodes lane `lane` of wave groups wave and wave + 4.
+__global__ void __launch_bounds__(kBlock)
+pack_rows_kernel(const double *__restrict__ A, uint64_t lda, uint64_t ncols, uint32_t ntiles, unsigned char *__restrict__ data,
+                 uint64_t *__restrict__ exc, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ info)
+{
+    typedef double dvec2 __attribute__((ext_vector_type(2)));
+    __shared__ uint32_t s_hist[kPackExpBins];
+    __shared__ uint32_t s_key[kWaves];
+    __shared__ uint32_t s_cnt;
+    __shared__ uint64_t s_exc[kPackCap];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t row = blockIdx.x;
+    const double *arow = A + row * lda;
+    unsigned long long row_exc = 0;
+    for (uint32_t tt = 0; tt < ntiles; tt++) {
+        const uint64_t c0 = (uint64_t)tt * kPackTile;
+        const uint32_t cols = (uint32_t)((ncols - c0 < (uint64_t)kPackTile) ? (ncols - c0) : (uint64_t)kPackTile);   // even
+        for (int i = tid; i < (int)kPackExpBins; i += kBlock) s_hist[i] = 0;
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        uint64_t v[2][8];
+        uint32_t valid = 0;                    // bit 4 h + s: the pair of step s in wave group wave + 4 h lies inside the row
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                const uint32_t col = (uint32_t)s * 1024u + (uint32_t)(wave + 4 * h) * 128u + 2u * (uint32_t)lane;
+                v[h][2 * s] = v[h][2 * s + 1] = 0;
+                if (col < cols) {
+                    const dvec2 a = __builtin_nontemporal_load(reinterpret_cast<const dvec2 *>(arow + c0 + col));
+                    v[h][2 * s] = (uint64_t)__double_as_longlong(a[0]);
+                    v[h][2 * s + 1] = (uint64_t)__double_as_longlong(a[1]);
+                    valid |= 1u << (4 * h + s);
+                }
+            }
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                if ((valid >> (4 * h + (e >> 1)) & 1u) && pack_is_normal(v[h][e])) atomicAdd(&s_hist[pack_exp_of(v[h][e])], 1u);
+        __syncthreads();
+        uint32_t key = 0;
+        for (uint32_t base = (uint32_t)tid * 8u; base < (uint32_t)tid * 8u + 8u; base++)
+            if (base >= 1u && base <= 2046u) key = max(key, pack_window_key(pack_window_count(s_hist, base), base));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, off, 64));
+        if (lane == 0) s_key[wave] = key;
+        __syncthreads();
+        key = s_key[0];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) key = max(key, s_key[w]);
+        const uint32_t base = key & 0x7ffu;
+
+        const uint64_t unit = row * ntiles + tt;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            uint32_t lo[8], mid[8], hi[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                if (!(valid >> (4 * h + (e >> 1)) & 1u)) pack_encode_exception(kPackZeroIdx, &lo[e], &mid[e], &hi[e]);
+                else if (pack_in_window(v[h][e], base)) pack_encode(v[h][e], base, &lo[e], &mid[e], &hi[e]);
+                else {
+                    const uint32_t idx = atomicAdd(&s_cnt, 1u);
+                    if (idx < kPackCap) s_exc[idx] = v[h][e];
+                    pack_encode_exception(idx < kPackCap ? idx : kPackZeroIdx, &lo[e], &mid[e], &hi[e]);
+                }
+            }
+            unsigned char *g = data + (unit * kPackGroups + (uint64_t)(wave + 4 * h)) * kPackGroupBytes;
+            pack_u4 q;
+            q[0] = lo[0]; q[1] = lo[1]; q[2] = lo[2]; q[3] = lo[3];
+            *reinterpret_cast<pack_u4 *>(g + pack_off_lo(lane, 0)) = q;
+            q[0] = lo[4]; q[1] = lo[5]; q[2] = lo[6]; q[3] = lo[7];
+            *reinterpret_cast<pack_u4 *>(g + pack_off_lo(lane, 4)) = q;
+            q[0] = mid[0] | mid[1] << 16; q[1] = mid[2] | mid[3] << 16; q[2] = mid[4] | mid[5] << 16; q[3] = mid[6] | mid[7] << 16;
+            *reinterpret_cast<pack_u4 *>(g + pack_off_mid(lane, 0)) = q;
+            pack_u2 b;
+            b[0] = hi[0] | hi[1] << 8 | hi[2] << 16 | hi[3] << 24;
+            b[1] = hi[4] | hi[5] << 8 | hi[6] << 16 | hi[7] << 24;
+            *reinterpret_cast<pack_u2 *>(g + pack_off_hi(lane, 0)) = b;
+        }
+        __syncthreads();
+        const uint32_t cnt = s_cnt;
+        for (uint32_t i = tid; i < cnt && i < kPackCap; i += kBlock) exc[unit * kPackCap + i] = s_exc[i];
+        if (tid == 0) {
+            hdr[unit] = pack_header(base, cnt);
+            row_exc += max(min(cnt, kPackCap), kPackFirst);
+            if (cnt > kPackCap) info[0] = 1ull;
+        }
+        __syncthreads();                       // s_cnt, s_exc and s_hist are free for the next tile
+    }
+    if (tid == 0) atomicAdd(&info[1], row_exc);
+}
+
+// The body of gemv_coop_kernel<double, double, 2, NT, 8> on the packed image: the same grid and reducer workgroup, the same rotated
+// tile order, s_p staging, lane-to-column mapping and fma sequence per lane (the +0 terms of a ragged tile included), the same
+// wave_sum, s_part order, store_y and publish_partial -- so the result is bit for bit the plain kernel's.  What differs is where an
+// element comes from: four coalesced non-temporal loads give a lane its 8 elements of a row and tile, the tile's exception values
+// are staged into LDS next to the p tile behind the same barrier (the first 64 of a list with the tile's other loads, the rest
+// of a longer list once the header has told its length), and every element is one LDS read of its (row, tile)'s list -- an exception's value, or the reserved +0.0 at one address for
+// the rest of the wave -- and a select: no branch per element.
+// One whole column segment [0, seg_end[0]) only (the launcher sends panels to the plain kernel).
+template <bool NT>
+__global__ void __launch_bounds__(512)
+gemv_packed_kernel(GemvArgs<double, double> a, PackedMat pk)
+{
+    constexpr int R = 2, WAVES = 8, TILE = kPackTile, STEP = 128, NTHREADS = WAVES * 64;
+    constexpr int WSTEPS = TILE / (STEP * WAVES);
+    static_assert(WSTEPS == 4 && STEP * WAVES == 1024, "the packed layout is that of 8 waves x 4 super-steps");
+
+    __shared__ __attribute__((aligned(16))) double s_p[TILE];
+    __shared__ double s_exc[R][kPackCap + 1];
+    __shared__ double s_part[R][WAVES];
+    __shared__ double s_dot[R];
+    __shared__ double s_red[kWaves];
+
+    if (a.sc != nullptr && a.sc->stop) return;
+    if (is_reducer_block(a.fin)) { reduce_partials(a.partial, (int)gridDim.x - 1, a.fin, s_red); return; }
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: a tile's addresses are scalar base + lane offset
+    const uint64_t row_first = (uint64_t)blockIdx.x * R;
+    const uint32_t woff = (uint32_t)wave * STEP + (uint32_t)lane * 2u;
+
+    const uint32_t ntiles = pk.ntiles;
+    uint64_t unit0[R];                          // the row's first (row, tile) unit
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        uint64_t row = row_first + r;
+        if (row >= a.nrows) row = a.nrows - 1;
+        unit0[r] = row * ntiles;
+    }
+    double acc[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.0;
+    if (tid < R) s_exc[tid][kPackZeroIdx] = 0.0;      // the reserved index; never overwritten (visible behind the first barrier)
+
+    constexpr uint32_t FIRST = kPackFirst;       // exception values staged before the header is known: one wave's load per row
+    static_assert(FIRST == 64, "one value a lane");
+    static_assert(R <= WAVES - 1, "waves 1 .. R stage the lists' first values");
+    const bool stager = wave >= 1 && wave <= R;
+    uint32_t perlane = 0;
+    asm volatile("" : "+v"(perlane));
+    uint32_t tt = blockIdx.x % ntiles;
+    for (uint32_t t = 0; t < ntiles; t++) {
+        const uint64_t c0 = (uint64_t)tt * TILE;
+        const uint64_t cend = a.seg_end[0];
+        const uint32_t cols = (uint32_t)((cend - c0 < (uint64_t)TILE) ? (cend - c0) : (uint64_t)TILE);
+        const uint32_t tnext = (tt + 1 == ntiles) ? 0 : tt + 1;
+        // the tile's elements: issued in front of the barriers (they depend on nothing the workgroup shares), so that they are in
+        // flight while p and the exception lists are staged
+        pack_u4 lo0[R], lo1[R], mid[R];
+        pack_u2 hi[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const unsigned char *g = pk.data + ((unit0[r] + tt) * kPackGroups + (uint64_t)wave) * kPackGroupBytes;
+            const pack_u4 *q0 = reinterpret_cast<const pack_u4 *>(g + pack_off_lo(lane, 0));
+            const pack_u4 *q1 = reinterpret_cast<const pack_u4 *>(g + pack_off_lo(lane, 4));
+            const pack_u4 *qm = reinterpret_cast<const pack_u4 *>(g + pack_off_mid(lane, 0));
+            const pack_u2 *qh = reinterpret_cast<const pack_u2 *>(g + pack_off_hi(lane, 0));
+            lo0[r] = NT ? __builtin_nontemporal_load(q0) : *q0;
+            lo1[r] = NT ? __builtin_nontemporal_load(q1) : *q1;
+            mid[r] = NT ? __builtin_nontemporal_load(qm) : *qm;
+            hi[r] = NT ? __builtin_nontemporal_load(qh) : *qh;
+        }
+        // ... and so are the headers and the first FIRST values of the exception lists (the lists have room for kPackCap values;
+        // what lies behind a list's count is never indexed): nothing the tile loads waits for another load
+        // (the headers are loaded per lane -- `perlane` is zero, but not to the compiler: as a wave-uniform value the header would
+        // be moved to a scalar register right behind its load, and the wave would wait there for every load in front of it)
+        uint32_t head[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) head[r] = pk.hdr[unit0[r] + tt + perlane];
+        double first = 0.0;
+        if (stager) first = pk.exc[(unit0[wave - 1] + tt) * kPackCap + lane];
+        __syncthreads();
+        {
+            typedef double pvec_t __attribute__((ext_vector_type(2)));
+            const pvec_t *src = reinterpret_cast<const pvec_t *>(a.p + c0);
+            pvec_t *dst = reinterpret_cast<pvec_t *>(s_p);
+            const uint32_t nv = cols / 2;
+            for (uint32_t i = tid; i < nv; i += NTHREADS) dst[i] = src[i];
+            for (uint32_t i = nv * 2 + tid; i < cols; i += NTHREADS) s_p[i] = a.p[c0 + i];
+            for (uint32_t i = cols + tid; i < (uint32_t)TILE && i < (cols + STEP * WAVES - 1) / (STEP * WAVES) * (STEP * WAVES); i += NTHREADS)
+                s_p[i] = 0.0;
+        }
+        uint32_t shift[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            shift[r] = pack_exp_shift(pack_header_base(head[r]));
+            if (stager && wave == 1 + r) s_exc[r][lane] = first;
+            const uint32_t cnt = min(pack_header_count(head[r]), kPackCap);
+            const double *e = pk.exc + (unit0[r] + tt) * kPackCap;
+            for (uint32_t i = FIRST + tid; i < cnt; i += NTHREADS) s_exc[r][i] = e[i];      // a long list: one more round trip
+        }
+        __syncthreads();
+        // whole tile: 4 super-steps; ragged last tile: ceil(cols / super-step) of them, the columns behind `cols` inside those
+        // decode to +0.0 (reserved index) and meet the zeros of the p tile -- the plain kernel's +0 terms
+        const int nsteps = (int)((cols + STEP * WAVES - 1) / (STEP * WAVES));
+#pragma unroll
+        for (int s = 0; s < WSTEPS; s++) {
+            if (s < nsteps) {
+                double pv[2];
+#pragma unroll
+                for (int i = 0; i < 2; i++) pv[i] = s_p[s * (STEP * WAVES) + woff + i];
+#pragma unroll
+                for (int r = 0; r < R; r++)
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const int e = 2 * s + i;
+                        const uint32_t l = e < 4 ? lo0[r][e & 3] : lo1[r][e & 3];
+                        const uint32_t w = ((hi[r][e >> 2] >> (8 * (e & 3))) & 0xffu) << 16 | ((mid[r][e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                        // every lane reads the list: its exception's value, or the reserved +0.0 (one address for the whole wave)
+                        const bool x = pack_is_exception(w);
+                        const double ev = s_exc[r][x ? min(l, kPackZeroIdx) : kPackZeroIdx];
+                        const double av = x ? ev : __longlong_as_double((long long)pack_decode(l, w, shift[r]));
+                        acc[r] = fma_tv(av, pv[i], acc[r]);
+                    }
+            }
+        }
+        tt = tnext;
+    }
+
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        double s = wave_sum(acc[r]);
+        if (lane == 0) s_part[r][wave] = s;
+    }
+    __syncthreads();
+    if (tid < R) {
+        const uint64_t row = row_first + tid;
+        double d = 0.0;
+        if (row < a.nrows) {
+            double s = s_part[tid][0];
 #pragma unroll
             for (int w = 1; w < WAVES; w++) s += s_part[tid][w];
             if (a.accumulate) s += a.y[row];

@@ -75,6 +75,10 @@ struct Impl {
         char buf[192];
         if (c->symv_active()) { snprintf(buf, sizeof buf, "symv_task_kernel<%s,NV=1> + symv_reduce_kernel<%s,NV=1>", ta, ta); return buf; }
         if (!fast_ok(c)) { snprintf(buf, sizeof buf, "gemv_generic_kernel<%s,%s>", ta, tv); return buf; }
+        if (c->pack_active()) {
+            snprintf(buf, sizeof buf, "gemv_packed_kernel<double,double,R=2,TILE=4096,NT=%s,WAVES=8>", c->opt_nt ? "true" : "false");
+            return buf;
+        }
         const int v = variant(c);
         const char *nt = c->opt_nt ? "true" : "false";
         if (v == 0) snprintf(buf, sizeof buf, "gemv_tile_kernel<%s,%s,R=4,TILE=4096,NT=%s,UNROLL=4,LDS=true,ROT=true>", ta, tv, nt);
@@ -182,6 +186,26 @@ struct Impl {
             if (a.nseg == 1) { a.seg_begin[1] = a.seg_end[1] = 0; }
         }
         const int grid = kernel_grid(c, s.nrows) + (a.fin.active ? 1 : 0);     // + the reducer workgroup (Finalize)
+        if constexpr (sizeof(TA) == 8) {
+            // the packed image (option "packed"): the whole product of the default shape only; panels read A
+            if (panel == 0 && c->pack_eligible()) {
+                PackState &pk = c->pack;
+                if (c->pack_active() && s.nrows <= pk.nrows) {
+                    const PackLayout L = pack_layout(pk.nrows, pk.ntiles);
+                    PackedMat m;
+                    m.data = (const unsigned char *)pk.buf + L.data;
+                    m.exc = (const double *)((const char *)pk.buf + L.exc);
+                    m.hdr = (const uint32_t *)((const char *)pk.buf + L.hdr);
+                    m.ntiles = (uint32_t)pk.ntiles;
+                    if (c->opt_nt) hipLaunchKernelGGL((gemv_packed_kernel<true>), dim3(grid), dim3(512), 0, s.stream, a, m);
+                    else hipLaunchKernelGGL((gemv_packed_kernel<false>), dim3(grid), dim3(512), 0, s.stream, a, m);
+                    LAUNCHED(c);
+                    return 0;
+                }
+                if (pk.count_gen != c->matrix_gen) { pk.count_gen = c->matrix_gen; pk.plain = 0; }
+                pk.plain++;
+            }
+        }
         if (fast_ok(c)) {
             switch (variant(c)) {
             default:
@@ -205,6 +229,72 @@ struct Impl {
         return 0;
     }
 };
+
+// Option "packed": build the packed image of the current matrix content in front of the next product when it is due -- value 1: now;
+// auto: once the content has served kPackAfter plain products, the matrix has at least kPackMinBytes and the device reports twice the
+// image free.  One pass of pack_rows_kernel on the shard's stream, outside every timing event pair (its callers sit in front of
+// the product step).  Never an error of its own: no memory, or a (row, tile) with more than kPackCap exceptions, and the plain
+// kernel goes on running for this content.
+int set_dev(lam_hip_ctx *c, const ShardBase &s);
+int pack_maybe(lam_hip_ctx *c)
+{
+    if (!c->pack_eligible() || !c->have_matrix) return 0;
+    PackState &pk = c->pack;
+    if (pk.ready_gen == c->matrix_gen || pk.refused_gen == c->matrix_gen) return 0;
+    ShardBase &s = c->sh[0];
+    const bool automatic = c->opt_packed < 0;
+    if (automatic) {
+        if (pk.count_gen != c->matrix_gen || pk.plain < (uint64_t)kPackAfter) return 0;
+        if (s.nrows * c->lda * 8ull < kPackMinBytes) return 0;
+    }
+    const uint64_t ncols = c->ncols_vec();
+    const uint64_t ntiles = (ncols + kPackTile - 1) / kPackTile;
+    const PackLayout L = pack_layout(s.nrows, ntiles);
+    const size_t need = L.total + 256;                      // + the pass's two result words
+    LAMCHK(set_dev(c, s));
+    if (pk.cap < need) {
+        if (automatic) {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+            if (free_b + pk.cap < 2 * need) { pk.refused_gen = c->matrix_gen; return 0; }
+        }
+        HIPCHK(c, hipStreamSynchronize(s.stream));
+        if (pk.buf != nullptr) { (void)hipFree(pk.buf); pk.buf = nullptr; pk.cap = 0; }
+        if (hipMalloc(&pk.buf, need) != hipSuccess) {
+            (void)hipGetLastError();
+            pk.buf = nullptr;
+            pk.refused_gen = c->matrix_gen;
+            return 0;
+        }
+        pk.cap = need;
+    }
+    pk.ready_gen = ~0ull;
+    pk.nrows = s.nrows; pk.ntiles = ntiles;
+    unsigned long long *info = (unsigned long long *)((char *)pk.buf + L.total);
+    unsigned long long got[2] = {0, 0};
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    const double t0 = now_s();
+    HIPCHK(c, hipMemsetAsync(info, 0, 16, s.stream));
+    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)s.nrows), dim3(kBlock), 0, s.stream, (const double *)s.A, c->lda, ncols, (uint32_t)ntiles,
+                       (unsigned char *)pk.buf + L.data, (uint64_t *)((char *)pk.buf + L.exc), (uint32_t *)((char *)pk.buf + L.hdr), info);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(got, info, 16, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    pk.pack_s = now_s() - t0;
+    if (got[0] != 0) { pk.refused_gen = c->matrix_gen; return 0; }
+    pk.exc_total = got[1];
+    pk.ready_gen = c->matrix_gen;
+    return 0;
+}
+
+// bytes one product of the shard reads: the plain kernel's, or the packed image's elements, headers and exception-list values
+double gemv_bytes_now(const lam_hip_ctx *c, const ShardBase &s0)
+{
+    const double vec = (double)c->esz_v() * (double)(c->n + s0.nrows);
+    if (!c->pack_active()) return (double)c->esz_a() * (double)s0.nrows * (double)c->n + vec;
+    const double units = (double)s0.nrows * (double)c->pack.ntiles;
+    return units * (double)(kPackTileBytes + 4) + 8.0 * (double)c->pack.exc_total + vec;
+}
 
 // The typed bodies of the host code are written as generic lambdas over Impl<TA,TV>; TA / TV are recovered with this small trait.
 template <typename T> struct ImplTraits;

@@ -57,6 +57,8 @@ extern "C" {
  *      CG batch call while a negative shift (which only lam_hip_solve_many_minres accepts) is in force.
  *      Added under version 4 likewise (purely additive): option "symmetric_many" and the get-only option "symmetric_many_effective".
  *      With "symmetric_many" at its default 0 every result is what it was.
+ *      Added under version 4 likewise (purely additive): option "packed" and the get-only options "packed_effective", "packed_bytes"
+ *      and "packed_pack_ns".  Every result is bit for bit what it was, under every value of the option.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_LANCZOS, LAM_HIP_EIG_SMALLEST / _LARGEST / _BOTH, lam_hip_eigs,
  *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_DEFLATION, lam_hip_set_deflation, lam_hip_set_deflation_eigs,
@@ -730,6 +732,22 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *                   environment variable, no automatic check.  One shard, fp64 / fp32, as the batch itself.
  *                   "symmetric_many_effective" (get): 1 if the last batched product launch ran the symmetric kernels, else 0
  *                   (before the first batched product, at K = 8, under value 1 below the threshold).
+ *   "packed"        the fp64 general product reads a LOSSLESS 7-byte-per-element image of the matrix instead of A:
+ *                   the same bits from 0.89 of the HBM traffic.  -1 (default) = automatic: a matrix content of 8 GiB or more is
+ *                   packed (one pass over A, 16 ms at N = 65536) in front of the next product once it has served 65 plain
+ *                   products, if the device reports twice the image's size free; 0 = never; 1 = pack in front of the next
+ *                   product.  Any other value: LAM_HIP_EINVAL.  Scope: LAM_HIP_F64, one shard, not rank mode, "symmetric" = 0,
+ *                   "gemv_variant" = -1, "force_generic" = 0, the whole product (lam_hip_gemv, lam_hip_gemv_only, the
+ *                   iteration's and the residual's product; column panels read A); everything else runs as before.  A stays in
+ *                   place and every other path reads it; the image (about 0.94 of A's size, grow-only, kept until
+ *                   lam_hip_destroy) follows the matrix content: an upload or a generator voids it.  A content with more than
+ *                   256 elements of one row and 4096-column tile outside that tile's best window of 7 binades (zero-heavy
+ *                   matrices: tridiagonal, heat) is not packable, and a refused allocation is not an error: the plain kernel
+ *                   runs.  Results are bit for bit those of the plain kernel, so a switch in the middle of a solve is invisible.
+ *                   "packed_effective" (get): 1 if the next product of the context reads the image, else 0;
+ *                   "packed_bytes" (get): the bytes one product then reads (0 when not effective) -- stats.gemv_bytes and
+ *                   lam_hip_gemv_kernel_name ("gemv_packed_kernel<...>") report the same kernel;
+ *                   "packed_pack_ns" (get): what the last pack took (0 when not effective).
  *   "symmetric"     the product reads every pair {A[i][j], A[j][i]} ONCE (A must equal its transpose): half the HBM traffic.
  *                   One shard: the upper triangle; several (exchange 1): cyclic half windows per row, each shard contributes
  *                   a full-length vector to the exchange.  1 = where it pays (from 192 MiB of matrix on), 2 = always, 0
