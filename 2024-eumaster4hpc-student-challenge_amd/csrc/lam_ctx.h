@@ -231,6 +231,8 @@ struct lam_hip_ctx {
     PcgState pcg;
     PackState pack;
     int64_t opt_packed = -1;       // fp64 general product on the packed image: -1 auto, 0 never, 1 pack in front of the next product
+    int64_t opt_packed_after = kPackAfter;                  // testing: auto's two thresholds (plain products served, bytes of matrix),
+    int64_t opt_packed_min_bytes = (int64_t)kPackMinBytes;  // so that the switch runs at sizes a test can afford
     int dtype = LAM_HIP_F64;
     int total_shards = 1;          // P
     int rank = 0, nranks = 1;      // rank mode (one local shard == shard `rank`)

@@ -1099,6 +1099,10 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
             return fail(c, LAM_HIP_EINVAL, "packed = %lld: -1 (automatic), 0 (never) or 1 (pack in front of the next product)", (long long)value);
         c->opt_packed = value;
     }
+    else if (!strcmp(name, "packed_after") || !strcmp(name, "packed_min_bytes")) {
+        if (value < 0) return fail(c, LAM_HIP_EINVAL, "%s = %lld: a count / a number of bytes, not negative", name, (long long)value);
+        (!strcmp(name, "packed_after") ? c->opt_packed_after : c->opt_packed_min_bytes) = value;
+    }
     else if (!strcmp(name, "gemv_timing")) c->opt_gemv_timing = value < 0 ? 0 : value;
     else if (!strcmp(name, "verify_direct")) c->opt_verify_direct = value;
     else if (!strcmp(name, "assume_cus")) { c->opt_assume_cus = value; c->cg_ready = false; }
@@ -1151,6 +1155,8 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "symmetric")) *value = c->opt_symmetric;
     else if (!strcmp(name, "symmetric_many")) *value = c->opt_symmetric_many;
     else if (!strcmp(name, "packed")) *value = c->opt_packed;
+    else if (!strcmp(name, "packed_after")) *value = c->opt_packed_after;
+    else if (!strcmp(name, "packed_min_bytes")) *value = c->opt_packed_min_bytes;
     else if (!strcmp(name, "packed_effective")) *value = c->pack_active() ? 1 : 0;
     else if (!strcmp(name, "packed_bytes")) *value = c->pack_active() ? (int64_t)gemv_bytes_now(c, c->sh[0]) : 0;
     else if (!strcmp(name, "packed_pack_ns")) *value = c->pack_active() ? (int64_t)(c->pack.pack_s * 1e9) : 0;

@@ -231,8 +231,8 @@ struct Impl {
 };
 
 // Option "packed": build the packed image of the current matrix content in front of the next product when it is due -- value 1: now;
-// auto: once the content has served kPackAfter plain products, the matrix has at least kPackMinBytes and the device reports twice the
-// image free.  One pass of pack_rows_kernel on the shard's stream, outside every timing event pair (its callers sit in front of
+// auto: once the content has served kPackAfter plain products, the matrix has at least kPackMinBytes (testing options "packed_after" /
+// "packed_min_bytes" move the two) and the device reports twice the image free.  One pass of pack_rows_kernel on the shard's stream, outside every timing event pair (its callers sit in front of
 // the product step).  Never an error of its own: no memory, or a (row, tile) with more than kPackCap exceptions, and the plain
 // kernel goes on running for this content.
 int set_dev(lam_hip_ctx *c, const ShardBase &s);
@@ -244,8 +244,8 @@ int pack_maybe(lam_hip_ctx *c)
     ShardBase &s = c->sh[0];
     const bool automatic = c->opt_packed < 0;
     if (automatic) {
-        if (pk.count_gen != c->matrix_gen || pk.plain < (uint64_t)kPackAfter) return 0;
-        if (s.nrows * c->lda * 8ull < kPackMinBytes) return 0;
+        if (pk.count_gen != c->matrix_gen || pk.plain < (uint64_t)c->opt_packed_after) return 0;
+        if (s.nrows * c->lda * 8ull < (uint64_t)c->opt_packed_min_bytes) return 0;
     }
     const uint64_t ncols = c->ncols_vec();
     const uint64_t ntiles = (ncols + kPackTile - 1) / kPackTile;

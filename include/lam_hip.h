@@ -58,7 +58,8 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): option "symmetric_many" and the get-only option "symmetric_many_effective".
  *      With "symmetric_many" at its default 0 every result is what it was.
  *      Added under version 4 likewise (purely additive): option "packed" and the get-only options "packed_effective", "packed_bytes"
- *      and "packed_pack_ns".  Every result is bit for bit what it was, under every value of the option.
+ *      and "packed_pack_ns".  Every result is bit for bit what it was, under every value of the option.  Likewise the testing
+ *      options "packed_after" and "packed_min_bytes" (defaults: what the automatic mode did before they existed).
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_LANCZOS, LAM_HIP_EIG_SMALLEST / _LARGEST / _BOTH, lam_hip_eigs,
  *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_DEFLATION, lam_hip_set_deflation, lam_hip_set_deflation_eigs,
@@ -769,6 +770,10 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *                   workgroup (faster at exactly 16 column tiles only); 0, 10 and 13 may be named as well.  20 / 21 (MFMA-fed,
  *                   bf16 storage): tuning build.  Any other number: LAM_HIP_EINVAL.
  *   "nt_loads" 1, "force_generic" 0, "probe_rows", "panel_lo"/"panel_hi"   kernel-level switches for tests and probes.
+ *   "packed_after" 65, "packed_min_bytes" 8 GiB   testing, as "assume_cus" / "panel_lo": the two thresholds of "packed" = -1
+ *                   (plain products a content serves before it is packed; bytes of matrix from which on), so that the automatic
+ *                   switch runs at a size a test can afford.  Negative: LAM_HIP_EINVAL.  No result depends on them; the
+ *                   free-memory rule is not theirs to move.
  *   "reuse_matrix"  1 (default) = lam_hip_set_problem keeps the matrix allocation when it is large enough (grow-only).
  *   "upload_staging" 1 = lam_hip_upload_rows copies through two pinned staging buffers (default 0: measured slower).
  *   get only: "row_pitch" (elements between rows on the device), "collectives_enqueued", "rccl_ranks" (ncclCommCount of
