@@ -463,6 +463,34 @@ class ConjugateGradient_HIP_base : public ConjugateGradient<FloatingType>
         return true;
     }
 
+    // Lanczos quadrature for the batch (lam_hip_lanczos_many, lam_hip_trace_quadrature): `steps` steps of plain Lanczos from nprobes
+    // probes -- Z holds them, probe j at Z + j * cols, or is null for Rademacher probes built on the device from `seed` -- groups of
+    // probes sharing each pass over the matrix.  steps_run / znorm2: nprobes entries, alpha / beta: nprobes * steps, any may be null;
+    // the context keeps them for trace_quadrature.  Returns true iff every coefficient is finite; batch_failed() as for solve_many.
+    bool lanczos_many(int nprobes, const FloatingType *Z, uint64_t seed, int steps, int32_t *steps_run = nullptr, double *znorm2 = nullptr,
+                      double *alpha = nullptr, double *beta = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        lam_hip_stats st;
+        if (lam_hip_lanczos_many(_ctx, nprobes, Z, seed, steps, &st, steps_run, znorm2, alpha, beta) != 0) return report("lanczos_many");
+        _stats = st;
+        _batch_failed = false;
+        return st.converged != 0;
+    }
+    // estimate[s] and std_error[s] of tr f(A + sigma_s I) from the last lanczos_many -- fn = LAM_HIP_QUAD_LOG (log det), _INV or _POW
+    // with exponent param; sigma null with nshifts == 1: no shift -- and, if per_probe is not null, the nshifts * nprobes values the
+    // mean is taken over.  Host arithmetic.
+    bool trace_quadrature(int fn, double param, int nshifts, const double *sigma, double *estimate, double *std_error,
+                          double *per_probe = nullptr)
+    {
+        _batch_failed = true;
+        if (!ensure_ctx()) return false;
+        if (lam_hip_trace_quadrature(_ctx, fn, param, nshifts, sigma, estimate, std_error, per_probe) != 0) return report("trace_quadrature");
+        _batch_failed = false;
+        return true;
+    }
+
     // Deflated CG for the batch (lam_hip_set_deflation*, lam_hip_solve_many_deflated): the residuals of solve_many_deflated stay
     // orthogonal to the space W, so the eigenvalues W captures no longer count.  set_deflation: W holds m vectors of get_num_cols()
     // elements, vector i at W + i * cols (m == 0 clears the space); set_deflation_from_eigs: the first m Ritz vectors of the last

@@ -8,6 +8,6 @@ gfx950 GPU, every compute call raises.
 from ._capi import (  # noqa: F401
     LamHipError, Stats, Solver, build, lib, lib_path, device_count, get_unique_id, partition, rccl_version, symv_plan_check,
     F64, F32, BF16, TUNING_LIB, MAX_RHS, MAX_SHIFTS, PC_NONE, PC_JACOBI, rhs_groups, MAX_LANCZOS, tridiag_eigen,
-    MAX_DEFLATION, chol_inverse, block_factor,
+    MAX_DEFLATION, chol_inverse, block_factor, MAX_PROBES, QUAD_FN, tridiag_quadrature,
 )
 from ._rendezvous import Rendezvous, launched_with_ranks  # noqa: F401,E402

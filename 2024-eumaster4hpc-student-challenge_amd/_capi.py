@@ -20,6 +20,8 @@ MAX_RHS = 8         # include/lam_hip.h LAM_HIP_MAX_RHS
 MAX_SHIFTS = 64     # include/lam_hip.h LAM_HIP_MAX_SHIFTS
 MAX_LANCZOS = 256   # include/lam_hip.h LAM_HIP_MAX_LANCZOS
 MAX_DEFLATION = 32  # include/lam_hip.h LAM_HIP_MAX_DEFLATION
+MAX_PROBES = 64     # include/lam_hip.h LAM_HIP_MAX_PROBES
+QUAD_FN = {"log": 0, "inv": 1, "pow": 2}   # include/lam_hip.h LAM_HIP_QUAD_*
 EIG_WHICH = {"smallest": 0, "largest": 1, "both": 2}   # include/lam_hip.h LAM_HIP_EIG_*
 PC_NONE, PC_JACOBI = 0, 1   # include/lam_hip.h LAM_HIP_PC_*: preconditioner of Solver.solve_many / solve_all
 _VEC_DTYPE = {F64: np.float64, F32: np.float32, BF16: np.float32}
@@ -154,6 +156,14 @@ def lib():
             "lam_hip_project_out": ([vp, u64, i32, vp, vp, C.POINTER(C.c_double)], i32),
             "lam_hip_tridiag_eigen": ([i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "lam_hip_lanczos_many": ([vp, i32, vp, u64, i32, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "lam_hip_get_lanczos_many": ([vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "lam_hip_trace_quadrature": ([vp, i32, C.c_double, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "lam_hip_tridiag_quadrature": ([i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, C.c_double, i32,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)], i32),
             "lam_hip_set_deflation": ([vp, i32, vp], i32),
             "lam_hip_set_deflation_eigs": ([vp, i32], i32),
             "lam_hip_solve_many_deflated": ([vp, i32, C.c_double, C.POINTER(Stats), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -240,6 +250,33 @@ def tridiag_eigen(alpha, beta, vectors=False):
     if rc != 0:
         raise LamHipError(rc, "lam_hip_tridiag_eigen: k outside 1..MAX_LANCZOS or a non-finite entry")
     return (theta[:k], row[:k], S.T.copy()) if vectors else (theta[:k], row[:k])
+
+
+def tridiag_quadrature(alpha, beta, fn, shifts=None, param=0):
+    """e_1^T f(T + s I) e_1 for every s of `shifts` (None: the one shift 0), T the symmetric tridiagonal matrix with diagonal alpha[k]
+    and off-diagonal beta[:k-1] (lam_hip_tridiag_quadrature: host only, no GPU, the routine Solver.trace_quadrature calls).  fn: "log",
+    "inv", "pow" (or the LAM_HIP_QUAD_* value); param: the exponent of "pow".  A refusal raises LamHipError; where a node was refused
+    its `bad` attribute is (shift, node)."""
+    f = QUAD_FN[fn] if isinstance(fn, str) else int(fn)
+    a = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    k = a.size
+    b = np.zeros(max(k, 1), np.float64)
+    bb = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+    if bb.size < k - 1:
+        raise ValueError("tridiag_quadrature: beta needs at least len(alpha) - 1 entries")
+    b[:max(k - 1, 0)] = bb[:max(k - 1, 0)]
+    dp = C.POINTER(C.c_double)
+    sg = None if shifts is None else np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+    ns = 1 if sg is None else sg.size
+    out = np.zeros(max(ns, 1), np.float64)
+    bad = (C.c_int * 2)(-1, -1)
+    rc = lib().lam_hip_tridiag_quadrature(k, a.ctypes.data_as(dp), b.ctypes.data_as(dp), f, float(param), ns,
+                                          None if sg is None else sg.ctypes.data_as(dp), out.ctypes.data_as(dp), bad)
+    if rc != 0:
+        e = LamHipError(rc, (lib().lam_hip_last_error(None) or b"").decode())
+        e.bad = (bad[0], bad[1])
+        raise e
+    return out[:ns]
 
 
 def chol_inverse(G):
@@ -714,6 +751,63 @@ class Solver:
         dp = C.POINTER(C.c_double)
         self._chk(self._L.lam_hip_get_lanczos(self._h, C.byref(ns), a.ctypes.data_as(dp), b.ctypes.data_as(dp)))
         return a[:ns.value].copy(), b[:ns.value].copy()
+
+    # -- Lanczos quadrature for the batch (one shard, F64 / F32) ----------------------------------
+    def lanczos_many(self, probes, steps, seed=0):
+        """`steps` steps of plain Lanczos from every probe, groups of probes sharing each pass over the matrix (lam_hip_lanczos_many).
+        probes: an int -- that many Rademacher probes built on the device from `seed` -- or an array of probe vectors of N elements
+        each, one per row.  Returns a dict: steps_run (nprobes), znorm2 (nprobes), alpha and beta (nprobes, steps; NaN past
+        steps_run), stats."""
+        zp = None
+        if isinstance(probes, (int, np.integer)):
+            nprobes = int(probes)
+        else:
+            Z = self._as_columns(probes)
+            nprobes, zp = Z.shape[0], Z.ctypes.data_as(C.c_void_p)
+        k, m = max(nprobes, 1), max(int(steps), 1)
+        sr, zz = np.zeros(k, np.int32), np.zeros(k, np.float64)
+        a, b = np.zeros((k, m), np.float64), np.zeros((k, m), np.float64)
+        st = Stats()
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lam_hip_lanczos_many(self._h, nprobes, zp, seed, steps, C.byref(st), sr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               zz.ctypes.data_as(dp), a.ctypes.data_as(dp), b.ctypes.data_as(dp)))
+        self.stats = st.asdict()
+        self.nprobes = nprobes
+        return {"steps_run": sr, "znorm2": zz, "alpha": a, "beta": b, "stats": self.stats}
+
+    def lanczos_many_coefficients(self, nprobes=None):
+        """What the last lanczos_many left in the context (lam_hip_get_lanczos_many): the same dict without the stats."""
+        k = int(getattr(self, "nprobes", 1) if nprobes is None else nprobes)
+        sr, zz = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.float64)
+        ns = C.c_int32(0)
+        dp = C.POINTER(C.c_double)
+        # the library lays the rows out at the run's own `steps`: ask for it first, then read into arrays of that shape
+        self._chk(self._L.lam_hip_get_lanczos_many(self._h, k, C.byref(ns), None, None, None, None))
+        a, b = np.zeros((k, ns.value), np.float64), np.zeros((k, ns.value), np.float64)
+        self._chk(self._L.lam_hip_get_lanczos_many(self._h, k, C.byref(ns), sr.ctypes.data_as(C.POINTER(C.c_int32)), zz.ctypes.data_as(dp),
+                                                   a.ctypes.data_as(dp), b.ctypes.data_as(dp)))
+        return {"steps_run": sr, "znorm2": zz, "alpha": a, "beta": b}
+
+    def trace_quadrature(self, fn, shifts=None, param=0, per_probe=False):
+        """The quadrature of the last lanczos_many for every shift (None: the one shift 0) -- host arithmetic
+        (lam_hip_trace_quadrature).  fn: "log", "inv", "pow" (or the LAM_HIP_QUAD_* value).  Returns (estimate, std_error), each one
+        entry per shift, and with per_probe=True also the (nshifts, nprobes) values the mean is taken over.  For Rademacher probes
+        estimate[s] estimates tr f(A + shifts[s] I)."""
+        f = QUAD_FN[fn] if isinstance(fn, str) else int(fn)
+        dp = C.POINTER(C.c_double)
+        sg = None if shifts is None else np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        ns = 1 if sg is None else sg.size
+        est, se = np.zeros(max(ns, 1), np.float64), np.zeros(max(ns, 1), np.float64)
+        pp = np.zeros((max(ns, 1), max(getattr(self, "nprobes", 1), 1)), np.float64)
+        self._chk(self._L.lam_hip_trace_quadrature(self._h, f, float(param), ns, None if sg is None else sg.ctypes.data_as(dp),
+                                                   est.ctypes.data_as(dp), se.ctypes.data_as(dp), pp.ctypes.data_as(dp) if per_probe else None))
+        return (est[:ns], se[:ns], pp[:ns]) if per_probe else (est[:ns], se[:ns])
+
+    def logdet(self, shifts=None, nprobes=8, steps=64, seed=0):
+        """(estimate, std_error) of log det(A + s I) for every s of `shifts` (None: log det A) from ONE run of nprobes Rademacher probes
+        and `steps` Lanczos steps (lanczos_many + trace_quadrature); steps is capped at min(N, MAX_LANCZOS)."""
+        self.lanczos_many(int(nprobes), min(int(steps), self.n, MAX_LANCZOS), seed)
+        return self.trace_quadrature("log", shifts)
 
     # -- deflated CG for the batch (one shard, F64 / F32) -----------------------------------------
     def set_deflation(self, W):

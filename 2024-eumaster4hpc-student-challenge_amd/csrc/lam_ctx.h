@@ -149,10 +149,23 @@ struct BlockState {
     BlockScalars *sc = nullptr;  // device; the last of the three to be allocated: set means all are
 };
 
+// lam_hip_lanczos_many (lam_quad.h): the device block of the batched Lanczos quadrature (scalars and the coefficient history of one
+// group), allocated by the first call for the batch's n and released with the batch (multi_release); its vectors are the batch's own.
+// What the host keeps of the last run is what lam_hip_get_lanczos_many and lam_hip_trace_quadrature serve: host data, which no other
+// batch call touches.
+struct QuadState {
+    QuadScalars *sc = nullptr;   // device
+    bool valid = false;          // the coefficients are readable: cleared by a new matrix content and by lam_hip_set_problem
+    int nprobes = 0, steps = 0;  // of the last run
+    std::vector<int32_t> steps_run;           // [nprobes]
+    std::vector<double> znorm2, alpha, beta;  // [nprobes]; [nprobes][steps] each, NaN past steps_run
+};
+
 struct MultiState {
     LanczosState lz;
     DeflateState df;
     BlockState bk;
+    QuadState qd;
     uint64_t n = 0;             // the problem size the buffers were allocated for (0: none)
     void *B = nullptr, *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;   // (n + 16) * kMaxRhs elements; P zero behind n
     void *stage = nullptr;       // n * kMaxRhs elements: the host interface's layout (column j contiguous) on its way in or out
@@ -420,7 +433,7 @@ void matrix_changed(lam_hip_ctx *c)
     c->cg_ready = false;
     c->matrix_gen++;
     c->sym_refused = false;
-    c->multi.solved = c->multi.ms.valid = c->multi.lz.valid = false;
+    c->multi.solved = c->multi.ms.valid = c->multi.lz.valid = c->multi.qd.valid = false;
 }
 
 // ConjugateGradient_CPU_MPI_OMP.hpp:176-184: n/P rows each, the remainder on the LAST rank (lam_host_plan.h)

@@ -50,6 +50,7 @@ using namespace lam;
 #include "lam_iterate.h"
 #include "lam_multi.h"
 #include "lam_eigs.h"
+#include "lam_quad.h"
 #include "lam_deflate.h"
 #include "lam_block.h"
 
@@ -214,7 +215,7 @@ int lam_hip_set_problem(lam_hip_ctx *c, uint64_t n)
     if (n < (uint64_t)c->total_shards) return fail(c, LAM_HIP_EINVAL, "n (%llu) smaller than the number of shards", (unsigned long long)n);
     // the batch state of lam_hip_solve_many belongs to one n: a new n releases it, the same n keeps the buffers (not the contents)
     if (n != c->multi.n) multi_release(c);
-    c->multi.have_rhs = c->multi.solved = c->multi.ms.valid = c->multi.lz.valid = false;
+    c->multi.have_rhs = c->multi.solved = c->multi.ms.valid = c->multi.lz.valid = c->multi.qd.valid = false;
     multi_clear_shifts(c->multi);
     c->n = n;
     c->iter_est_s = 0.0;           // the observed iteration time belongs to the previous problem

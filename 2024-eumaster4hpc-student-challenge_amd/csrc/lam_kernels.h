@@ -45,6 +45,7 @@
 #include "lam_host_plan.h"
 #include "lam_host_pack.h"
 #include "lam_host_tridiag.h"
+#include "lam_host_quad.h"
 #include "lam_host_chol.h"
 #include "lam_host_block.h"
 
@@ -3221,6 +3222,226 @@ minres_update_kernel(const double *__restrict__ red, int nred, MinresScalars *sc
                 VOLD[e] = vi;
                 V[e] = U[e] * ibeta[j];
             }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched Lanczos quadrature (lam_hip_lanczos_many, lam_quad.h): K independent plain Lanczos recurrences on A -- three-term only, no
+// reorthogonalisation, no stored basis -- advanced together, from K probes.  Three launches per step: multi_gemv_kernel on V
+// (u = A v, partials of v.u), quad_three_term_kernel (alpha = v.u ; u -= alpha v + beta v_old ; partials of u.u) and
+// quad_next_kernel (beta' = sqrt(u.u), the history store, lam_hip_eigs' breakdown rule, v_old = v, v = u / beta').  The recurrence is
+// stated in include/lam_hip.h.  In front of the loop: quad_probe_kernel (the probes into V, partials of z.z),
+// quad_start_scalars_kernel and quad_start_kernel (v = z / ||z||, v_old = 0).
+// Vectors: V is the batch's P (the product's input: zero behind row n), U its AP, v_old its R.
+// Scalars: the MultiScalars prefix (what the product kernel reads) with col[j].alpha = the last v.u, .beta = the last beta', .iters,
+// .stop; behind it beta and the breakdown rule's scale in rings of two -- step k reads slot (k + 1) & 1, workgroup 0 writes slot
+// k & 1 (MinresScalars::rot's scheme) -- and the history [step][K] the host copies back once per group.
+// Who decides: minres_update_kernel's argument to the letter.  Every workgroup of quad_next_kernel recomputes a probe's beta' and
+// its breakdown decision from bits no workgroup of that launch writes; workgroup 0 alone stores.  frozen_at[j] is the first step in
+// which the probe does nothing (0: live; k + 1 for a breakdown at k; 1 for a padding column), so a workgroup that starts behind
+// workgroup 0's store reads "ran at k" as workgroup 0 did.  The launch does not return on all_stop, which its own workgroup 0
+// raises: it returns when no probe runs at k by frozen_at.  The product and quad_three_term_kernel keep the all_stop guard.
+// Coefficients that multiply vectors (alpha, beta, the reciprocals) are formed in fp64 and rounded to the vector dtype once; every
+// vector statement is an explicit fma_tv chain.
+// ---------------------------------------------------------------------------------------------
+struct QuadScalars : MultiScalars {
+    double zz[kMaxRhs];               // z.z of the probe as given
+    double beta[kMaxRhs][2];          // beta_k at [k & 1] (beta_0 = 0 in both slots at the start)
+    double tmax[kMaxRhs][2];          // max_{i <= k}(|alpha_i| + beta_{i-1} + beta_i) at [k & 1]
+    int frozen_at[kMaxRhs];           // 0: live; else the first step in which the probe does nothing
+    int steps_run[kMaxRhs];           // the last step the probe completed
+    double hist_alpha[kMaxLanczos * kMaxRhs];     // alpha_k of probe j at [(k - 1) * K + j], K the group's instantiation
+    double hist_beta[kMaxLanczos * kMaxRhs];
+};
+
+// The Rademacher law of the generated probes: z_j[i] = 1 - 2 (h >> 63), h = sm(seed ^ sm(0x51AC + j * n + i)), j the GLOBAL probe index
+__host__ __device__ __forceinline__ double quad_rademacher(uint64_t seed, uint64_t probe, uint64_t n, uint64_t i)
+{
+    const uint64_t h = splitmix64(seed ^ splitmix64(0x51ACull + probe * n + i));
+    return 1.0 - 2.0 * (double)(h >> 63);
+}
+
+// V = the probes: GENERATE the Rademacher law by global probe index first + j, else what the upload left in V; padding columns
+// (j >= count) zero; V's rows behind row n zero in this K's layout (minres_init_kernel); partials of z_j.z_j at [j * gridDim.x + block]
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+quad_probe_kernel(bool generate, int count, uint64_t first, uint64_t seed, TV *__restrict__ V, uint64_t n, double *__restrict__ partial)
+{
+    __shared__ double s_red[kWaves];
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = 0.0;
+    if (blockIdx.x == 0 && threadIdx.x < kMultiPadRows * K) V[n * K + threadIdx.x] = (TV)0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t e = i * K + j;
+            TV zi = (TV)0;
+            if (j < count) zi = generate ? (TV)quad_rademacher(seed, first + (uint64_t)j, n, i) : V[e];
+            V[e] = zi;
+            acc[j] += (double)zi * (double)zi;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// per probe: zz, the rings' start (beta_0 = 0, tmax = 0), iters = 0; live probes start running, padding columns are born stopped.
+// One workgroup.
+template <int K>
+__global__ void __launch_bounds__(kBlock)
+quad_start_scalars_kernel(const double *__restrict__ red, int nred, int count, QuadScalars *sc, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    for (int j = 0; j < kMaxRhs; j++) {
+        const double t = j < K ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        if (threadIdx.x == 0) {
+            CgScalars &c = sc->col[j];
+            c.bb = t; c.rr[0] = 0.0; c.rr[1] = 0.0; c.pAp = 0.0; c.alpha = 0.0; c.beta = 0.0; c.iters = 0;
+            c.stop = j < count ? 0 : 1;
+            sc->zz[j] = t;
+            sc->beta[j][0] = 0.0; sc->beta[j][1] = 0.0;
+            sc->tmax[j][0] = 0.0; sc->tmax[j][1] = 0.0;
+            sc->frozen_at[j] = j < count ? 0 : 1;
+            sc->steps_run[j] = 0;
+        }
+    }
+    if (threadIdx.x == 0) {
+        sc->pad = 0;
+        sc->all_stop = 0;
+        post_progress(host_flags, 0, false);
+    }
+}
+
+// v_j = z_j * (1 / sqrt(zz_j)) in place for the live probes (the padding columns are zero already) ; v_old = 0
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+quad_start_kernel(TV *__restrict__ V, TV *__restrict__ VOLD, uint64_t n, const QuadScalars *sc)
+{
+    TV iz[K];
+    bool live[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        live[j] = sc->frozen_at[j] == 0;
+        iz[j] = (TV)(1.0 / sqrt(sc->zz[j]));
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t e = i * K + j;
+            if (live[j]) V[e] = V[e] * iz[j];
+            VOLD[e] = (TV)0;
+        }
+    }
+}
+
+// vector launch 1, per running probe j: alpha = v_j.u_j from the product's partials ; u_j = fma(-beta, v_old_j, fma(-alpha, v_j, u_j)) ;
+// partials of u_j.u_j.  minres_lanczos_kernel's statement on this section's scalars.  No workgroup writes what another reads:
+// col[j].alpha is for the next launch.
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+quad_three_term_kernel(const double *__restrict__ red, int nred, QuadScalars *sc, int k, const TV *__restrict__ V,
+                       const TV *__restrict__ VOLD, TV *__restrict__ U, uint64_t n, double *__restrict__ partial)
+{
+    __shared__ double s_red[kWaves];
+    if (sc->all_stop) return;
+    bool run[K];
+    double alpha_d[K], acc[K];
+    TV nalpha[K], nbeta[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        run[j] = sc->col[j].stop == 0;
+        alpha_d[j] = run[j] ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        nalpha[j] = -(TV)alpha_d[j];
+        nbeta[j] = -(TV)sc->beta[j][(k + 1) & 1];
+        acc[j] = 0.0;
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (!run[j]) continue;
+            const uint64_t e = i * K + j;
+            const TV ui = fma_tv(nbeta[j], VOLD[e], fma_tv(nalpha[j], V[e], U[e]));
+            U[e] = ui;
+            acc[j] += (double)ui * (double)ui;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double t = block_sum(acc[j], s_red);
+        if (threadIdx.x == 0) {
+            partial[(size_t)j * gridDim.x + blockIdx.x] = t;
+            if (blockIdx.x == 0 && run[j]) { sc->col[j].pAp = alpha_d[j]; sc->col[j].alpha = alpha_d[j]; }
+        }
+    }
+}
+
+// vector launch 2, per running probe j: beta' = sqrt(u_j.u_j) ; alpha and beta' into the history ; the breakdown rule (beta' zero,
+// not finite or <= scale * max_i(|alpha_i| + beta_{i-1} + beta_i), scale = N * unit roundoff of the vector dtype): the probe stops,
+// v_j untouched; else v_old_j = v_j, v_j = u_j * (1 / beta').  The progress word reports the step, and "stopped" once EVERY live
+// probe has broken down.
+template <typename TV, int K>
+__global__ void __launch_bounds__(kBlock)
+quad_next_kernel(const double *__restrict__ red, int nred, QuadScalars *sc, int k, double scale, const TV *__restrict__ U,
+                 TV *__restrict__ V, TV *__restrict__ VOLD, uint64_t n, volatile int *host_flags)
+{
+    __shared__ double s_red[kWaves];
+    // NOT `if (sc->all_stop) return` (see minres_update_kernel): the launch is over only if no probe runs at k, which frozen_at says
+    // the same way before and after workgroup 0's store
+    bool run[K], adv[K];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const int fz = sc->frozen_at[j];
+        run[j] = fz == 0 || k < fz;
+        any = any || run[j];
+    }
+    if (!any) return;
+    TV ibeta[K];
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const double uu = run[j] ? block_sum_array(red + (size_t)j * nred, nred, s_red) : 0.0;
+        const double betan = sqrt(uu);
+        const double alpha = sc->col[j].alpha;                           // the three-term launch of this step wrote it
+        const double bprev = sc->beta[j][(k + 1) & 1], tprev = sc->tmax[j][(k + 1) & 1];
+        const double tmax = fmax(tprev, fabs(alpha) + bprev + betan);
+        const bool stop = !(betan > scale * tmax) || !(betan <= std::numeric_limits<double>::max());
+        adv[j] = run[j] && !stop;
+        all = all && !adv[j];
+        ibeta[j] = (TV)(1.0 / betan);
+        if (run[j] && blockIdx.x == 0 && threadIdx.x == 0) {
+            sc->beta[j][k & 1] = betan;
+            sc->tmax[j][k & 1] = tmax;
+            sc->col[j].beta = betan;
+            sc->col[j].iters = k;
+            sc->steps_run[j] = k;
+            sc->hist_alpha[(size_t)(k - 1) * K + j] = alpha;
+            sc->hist_beta[(size_t)(k - 1) * K + j] = betan;
+        }
+    }
+    if (blockIdx.x == 0) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                if (run[j] && !adv[j]) { sc->frozen_at[j] = k + 1; sc->col[j].stop = 1; }
+            if (all) sc->all_stop = 1;
+            post_progress(host_flags, k, all);
+        }
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (!adv[j]) continue;
+            const uint64_t e = i * K + j;
+            const TV vi = V[e];
+            VOLD[e] = vi;
+            V[e] = U[e] * ibeta[j];
         }
     }
 }

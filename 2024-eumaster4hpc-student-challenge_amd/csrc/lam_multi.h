@@ -64,6 +64,7 @@ void multi_release(lam_hip_ctx *c)
     free_dev({m.lz.V, m.lz.U, m.lz.Y, m.lz.part, m.lz.part_uu, m.lz.S, m.lz.sc});
     free_dev({m.df.W, m.df.AW, m.df.Ginv, m.df.part});
     free_dev({m.bk.part_h, m.bk.part_g, m.bk.sc});
+    free_dev({m.qd.sc});
     if (m.sc_host) (void)hipHostFree(m.sc_host);
     if (m.host_flags) (void)hipHostFree(m.host_flags);
     for (int i = 0; i < kLag; i++) {

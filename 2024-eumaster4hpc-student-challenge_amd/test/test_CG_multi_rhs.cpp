@@ -4,6 +4,7 @@
 //     test_CG_multi_rhs.out -s N -E nev [-W s|l|b] [-i max_steps] [-e tol] [-t f64|f32] [-Y 0|1|2]
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters -D m [-W s|l|b] [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters -B [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]
+//     test_CG_multi_rhs.out -s N -Q nprobes [-i steps] [-S s0,s1,...] [-t f64|f32] [-Y 0|1|2]
 // -J: Jacobi-preconditioned recurrences (lam_hip_solve_many_pc; off by default).  tridiag(1,2,1) has a constant diagonal, so the
 // iteration and residual columns are the plain ones digit for digit: the flag exercises the path, it does not save iterations here.
 // -w W: two stages (lam_hip_solve_many_x0): W iterations from x = 0, then a continuation from that solution (a fresh r = b - A x)
@@ -36,6 +37,12 @@
 // a block Krylov space of a few dimensions on this matrix), so column j is b_j[i] = 1 + (((i * 8 + j) * 2654435761) mod 2^32 >> 28).  The usual
 // CSV line per column (num_iters: the first iteration at which the column met the test); one line on STDERR gives the iterations
 // run and the breakdown pair.  -B with -J, -S, -M, -m, -D, -w or -E is a usage error.
+// -Q nprobes: Lanczos quadrature (lam_hip_lanczos_many + lam_hip_trace_quadrature) in place of a solve: nprobes (1..64) Rademacher
+// probes built on the device from seed 0, -i steps of plain Lanczos each (default min(N, 64)), and -S s0,s1,... (up to 64 finite
+// shifts; none: the one shift 0) as the shifts of the quadrature -- all of them from the ONE run.  One CSV line per shift:
+//     shift,logdet_estimate,logdet_std_error,trinv_estimate,trinv_std_error,steps,seconds
+// the estimates of log det(A + s I) and tr (A + s I)^-1 with their standard errors over the probes, the largest number of steps a
+// probe ran, and the seconds of the run and its quadratures.  -Q with -J, -w, -M, -m, -T, -k, -e, -E, -D or -B is a usage error.
 // Without these flags the calls and the output are those of the driver before them.
 // One CSV line per column in the format of the getopt drivers (test_CG_MultiGPUS_HIP_RCCL.cpp; the reference's
 // challenge/main/test/test_CG_CPU_MPI_OMP.cpp:196-206 plus the comm-init column, 0 here):
@@ -280,6 +287,36 @@ static int run_block(size_t rows, int nrhs, int max_iters, double rel_error, boo
     return 0;
 }
 
+// -Q: log det(A + s I) and tr (A + s I)^-1 of the generated matrix for every shift, from one run of nprobes Rademacher probes
+template <typename T>
+static int run_quadrature(size_t rows, int nprobes, int steps, const std::vector<double> &shifts, int sym)
+{
+    using clk = std::chrono::high_resolution_clock;
+    LAM::ConjugateGradient_HIP<T> cg(0);
+    cg.set_text_output(false);
+    if (!cg.generate_matrix(rows, rows)) {
+        fprintf(stderr, "Failed to generate matrix\n");
+        return 1;
+    }
+    if (!set_symmetric_many(cg.context(), sym)) return 3;
+    const int ns = shifts.empty() ? 1 : (int)shifts.size();
+    const double *sigma = shifts.empty() ? nullptr : shifts.data();
+    std::vector<double> ld(ns), ld_se(ns), ti(ns), ti_se(ns);
+    const auto t1 = clk::now();
+    cg.lanczos_many(nprobes, nullptr, 0, steps);
+    if (cg.batch_failed()) return 3;
+    const lam_hip_stats st = cg.stats();
+    report_symmetric_many(cg.context(), sym);
+    if (!cg.trace_quadrature(LAM_HIP_QUAD_LOG, 0.0, ns, sigma, ld.data(), ld_se.data())) return 3;
+    if (!cg.trace_quadrature(LAM_HIP_QUAD_INV, 0.0, ns, sigma, ti.data(), ti_se.data())) return 3;
+    const double t_q = std::chrono::duration<double>(clk::now() - t1).count();
+    std::cout.precision(17);
+    for (int j = 0; j < ns; j++)
+        std::cout << (sigma ? sigma[j] : 0.0) << "," << ld[j] << "," << ld_se[j] << "," << ti[j] << "," << ti_se[j] << "," << st.num_iters << ","
+                  << t_q << std::endl;
+    return 0;
+}
+
 // "s0,s1,...": 1..LAM_HIP_MAX_SHIFTS numbers (main holds a list without -M to LAM_HIP_MAX_RHS), each finite, nothing else; *negative:
 // one of them is < 0, which main accepts under -m only (it decides once every option is parsed)
 static bool parse_shifts(const char *arg, std::vector<double> *out, bool *negative)
@@ -307,6 +344,8 @@ int main(int argc, char **argv)
     int defl = 0;                                    // 0: no -D
     bool d_given = false;
     bool block = false;                              // -B
+    int nprobes = 0;                                 // -Q
+    bool q_given = false, e_given = false;
     bool bad_eigs = false, i_given = false, s_given = false;
     double rel_error = 1e-9;
     const char *precision = "f64";
@@ -316,12 +355,12 @@ int main(int argc, char **argv)
     bool bad_sym = false;
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:E:W:D:Bh")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:E:W:D:BQ:h")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
         case 'i': max_iters = atoi(optarg); i_given = true; break;
-        case 'e': rel_error = atof(optarg); break;
+        case 'e': rel_error = atof(optarg); e_given = true; break;
         case 't': precision = optarg; break;
         case 'J': jacobi = true; break;
         case 'w': warm = atoi(optarg); bad_warm = warm < 0; break;
@@ -332,6 +371,7 @@ int main(int argc, char **argv)
         case 'E': nev = atoi(optarg); bad_eigs = bad_eigs || nev < 1; break;
         case 'D': defl = atoi(optarg); d_given = true; break;
         case 'B': block = true; break;
+        case 'Q': nprobes = atoi(optarg); q_given = true; break;
         case 'W':
             if (!strcmp(optarg, "s")) which = LAM_HIP_EIG_SMALLEST;
             else if (!strcmp(optarg, "l")) which = LAM_HIP_EIG_LARGEST;
@@ -348,13 +388,32 @@ int main(int argc, char **argv)
                     "[-E nev (Lanczos eigensolver lam_hip_eigs in place of a solve: nev extreme eigenpairs; -W s|l|b smallest / largest / both, "
                     "-i max_steps up to %d, -e tol; not with -J, -w, -S, -M, -m, -k)] "
                     "[-D m (deflated CG on m = 1..%d Ritz pairs of lam_hip_eigs, -W s|l|b; not with -J, -w, -S, -M, -m, -E)] "
-                    "[-B (block CG lam_hip_solve_block: one block Krylov space for the nrhs columns; not with -J, -w, -S, -M, -m, -D, -E)]\n", argv[0],
-                    LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS, LAM_HIP_MAX_LANCZOS, LAM_HIP_MAX_DEFLATION);
+                    "[-B (block CG lam_hip_solve_block: one block Krylov space for the nrhs columns; not with -J, -w, -S, -M, -m, -D, -E)] "
+                    "[-Q nprobes (Lanczos quadrature lam_hip_lanczos_many in place of a solve: log det(A + s I) and tr (A + s I)^-1 for the "
+                    "shifts of -S from 1..%d Rademacher probes, -i steps each; not with -J, -w, -M, -m, -T, -k, -e, -E, -D, -B)]\n", argv[0],
+                    LAM_HIP_MAX_RHS, LAM_HIP_MAX_SHIFTS, LAM_HIP_MAX_LANCZOS, LAM_HIP_MAX_DEFLATION, LAM_HIP_MAX_PROBES);
             return opt == 'h' ? 0 : 1;
         }
     }
     if (bad_sym) {
         fprintf(stderr, "Usage: -Y takes 0 (the general batched product), 1 (the symmetric one where it pays) or 2 (always, up to 4 columns)\n");
+        return 1;
+    }
+    if (q_given) {
+        if (jacobi || warm >= 0 || bad_warm || mshift || minres || true_res || k_given || e_given || nev != 0 || bad_eigs || d_given || block) {
+            fprintf(stderr, "Usage: -Q takes neither -J, -w, -M, -m, -T, -k, -e, -E, -D nor -B: the quadrature runs on the matrix alone, -i are "
+                    "its steps and -S its shifts\n");
+            return 1;
+        }
+        if (!i_given) max_iters = (int)(rows < 64 ? rows : 64);
+        if (rows == 0 || nprobes < 1 || nprobes > LAM_HIP_MAX_PROBES || max_iters < 1 || bad_shifts) {
+            fprintf(stderr, "Usage: %s -s N -Q nprobes (1..%d) [-i steps (1..min(N, %d))] [-S s0,s1,... (up to %d finite shifts)] [-t f64|f32] "
+                    "[-Y 0|1|2]\n", argv[0], LAM_HIP_MAX_PROBES, LAM_HIP_MAX_LANCZOS, LAM_HIP_MAX_SHIFTS);
+            return 1;
+        }
+        if (!strcmp(precision, "f64")) return run_quadrature<double>(rows, nprobes, max_iters, shifts, sym);
+        if (!strcmp(precision, "f32")) return run_quadrature<float>(rows, nprobes, max_iters, shifts, sym);
+        fprintf(stderr, "Unknown precision '%s' (f64, f32)\n", precision);
         return 1;
     }
     if (block) {

@@ -64,7 +64,9 @@ extern "C" {
  *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_DEFLATION, lam_hip_set_deflation, lam_hip_set_deflation_eigs,
  *      lam_hip_solve_many_deflated, lam_hip_deflate_many, lam_hip_chol_inverse and the get-only option "deflation_m".
- *      Added under version 4 likewise (purely additive): lam_hip_solve_block and lam_hip_block_factor. */
+ *      Added under version 4 likewise (purely additive): lam_hip_solve_block and lam_hip_block_factor.
+ *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_PROBES, LAM_HIP_QUAD_LOG / _INV / _POW, lam_hip_lanczos_many,
+ *      lam_hip_get_lanczos_many, lam_hip_trace_quadrature and lam_hip_tridiag_quadrature. */
 #define LAM_HIP_ABI_VERSION 4
 
 /* most row shards of one process (lam_hip_create) / ranks of one communicator (lam_hip_create_rank); more -> LAM_HIP_EINVAL.
@@ -530,6 +532,86 @@ int lam_hip_eig_residuals(lam_hip_ctx *ctx, int nev, double *res);
  * carries the one row, O(k^2).  This is the routine lam_hip_eigs calls (csrc/lam_host_tridiag.h).  k outside
  * 1..LAM_HIP_MAX_LANCZOS, a NULL array or a non-finite entry: LAM_HIP_EINVAL. */
 int lam_hip_tridiag_eigen(int k, const double *alpha, const double *beta, double *theta, double *last_row, double *S);
+
+/* ---- Lanczos quadrature for the batch: log det(A + s I) and tr f(A) -----------------------------
+ * The second number next to every solve of a sweep: log det(A + s I) (the other half of a Gaussian marginal likelihood),
+ * tr (A + s I)^-1 (effective degrees of freedom, GCV), tr A^p.  Stochastic Lanczos quadrature (Golub & Meurant; Ubaru, Chen & Saad
+ * 2017): m steps of plain Lanczos from a probe z give z^T f(A) z ~ ||z||^2 e_1^T f(T_m) e_1, a Gauss rule that is exact for
+ * polynomials of degree 2m - 1; with Rademacher probes the mean over the probes estimates tr f(A).  Lanczos on A + s I from the same
+ * probe gives T + s I, so ONE run serves every shift of a sweep, on the host, in O(m^2) per shift.  No reference counterpart.
+ *
+ * lam_hip_lanczos_many runs nprobes <= LAM_HIP_MAX_PROBES independent recurrences on the context's matrix A -- the plain product, as
+ * lam_hip_eigs: the shifts in force are ignored -- with the three-term recurrence only: NO reorthogonalisation and NO stored basis
+ * (the quadrature tolerates the loss of orthogonality that ruins Ritz vectors: ghost eigenvalues carry the weight of the copies they
+ * stand for), nothing kept but 2 * steps doubles per probe.  Probes run in groups of up to 8 -- of up to 4 where option
+ * "symmetric_many" engages for K <= 4, lam_hip_set_deflation's grouping rule -- each at the smallest K in {1, 2, 4, 8} that holds
+ * it, padding columns zero and born stopped; a group shares one pass over A per step.
+ *   - per probe j, every scalar fp64, the coefficients that multiply vectors rounded to the vector dtype (TV) once, every vector
+ *     statement an explicit fma chain:
+ *         zz = z.z ; v = z * (TV)(1 / sqrt(zz)) ; v_old = 0 ; beta_0 = 0
+ *         k = 1 .. steps:
+ *            u = A v                                            the batch's product launch; alpha_k = v.u from its fused partials
+ *            u = fma(-beta_{k-1}, v_old, fma(-alpha_k, v, u))   vector launch 1; partials of u.u
+ *            beta_k = sqrt(u.u) ; store alpha_k, beta_k         vector launch 2
+ *            BREAKDOWN (lam_hip_eigs' rule: beta_k zero, not finite, or <= N u_TV max_{i <= k}(|alpha_i| + beta_{i-1} + beta_i)):
+ *                 the probe stops, steps_run = k (its Krylov space is invariant: the quadrature is exact)
+ *            else v_old = v ; v = u * (TV)(1 / beta_k)
+ *   - probes: z_host holds nprobes vectors of N elements of the vector dtype, probe j at z_host + j*N; a probe whose norm is zero or
+ *     not finite is LAM_HIP_EINVAL naming it.  z_host == NULL: Rademacher probes built on the device,
+ *     z_j[i] = 1 - 2 (h >> 63), h = sm(seed ^ sm(0x51AC + j*N + i)), sm SplitMix64 in wrapping uint64 as in the generators, j the
+ *     GLOBAL probe index and i the row (tests/quadrature_reference.py);
+ *   - outputs: steps_run[nprobes], znorm2[nprobes] (the device's z.z), alpha and beta with probe j's coefficients at + j*steps,
+ *     entries past steps_run[j] NaN.  Any output pointer may be NULL; the same data stays in the context -- host data, which no
+ *     other batch call touches -- for lam_hip_get_lanczos_many and lam_hip_trace_quadrature until the next lam_hip_lanczos_many, a new
+ *     matrix content or lam_hip_set_problem; otherwise LAM_HIP_ESTATE;
+ *   - stats: num_iters = the largest steps_run, converged = every stored coefficient is finite, rel_err = 0, t_gemv / t_iter /
+ *     t_total / gemv_bytes the batch's, for the last group's K;
+ *   - every sum goes through per-workgroup partials summed in a fixed order (no floating-point atomics): two identical calls give
+ *     identical bits, a probe's coefficients do not depend on its neighbours, and a NaN in one probe stays in its column;
+ *   - launches per step ("hip_calls_launch"): 3 per group -- the product and two vector launches --, 4 under "symmetric_many" at
+ *     K <= 4;
+ *   - state: the batch's P (v, the product's input), AP (u) and R (v_old), and a small device block of its own (scalars and one
+ *     group's coefficient history), allocated at the first call and released with the batch.  The right-hand sides, the shifts, the
+ *     deflation space, the eigen-solution and the single-vector state are left alone; a batched or multi-shift solution is no longer
+ *     readable afterwards (LAM_HIP_ESTATE), exactly as after lam_hip_gemv_many; "multi_rhs_k" reports the last group's K;
+ *   - refusals: what the batch refuses, with the same codes and words (several shards, rank mode, LAM_HIP_BF16); no matrix:
+ *     LAM_HIP_ESTATE; nprobes outside 1..LAM_HIP_MAX_PROBES, steps outside 1..min(N, LAM_HIP_MAX_LANCZOS): LAM_HIP_EINVAL naming
+ *     the value;
+ *   - out of scope: reorthogonalisation or a stored basis (lam_hip_eigs has both, for one vector); Gauss-Radau or other modified
+ *     rules; a function pointer for f; probes other than Rademacher generated on the device (a caller passes any others from the
+ *     host); an adaptive number of steps or probes; gradients of log det (they need solves, which the batch provides); several
+ *     shards, rank mode, bf16;
+ *   - cost: a step is the batch's product launch plus two latency-bound vector launches, the profile of lam_hip_solve_many_minres'
+ *     iteration; the ratio of the two has not been measured (tools/quadrature_probe.py, profiles/quadrature_probe.txt). */
+#define LAM_HIP_MAX_PROBES 64          /* 8 groups of LAM_HIP_MAX_RHS */
+#define LAM_HIP_QUAD_LOG 0             /* f(t) = log t */
+#define LAM_HIP_QUAD_INV 1             /* f(t) = 1 / t */
+#define LAM_HIP_QUAD_POW 2             /* f(t) = t^p, p = (int)param >= 0 */
+int lam_hip_lanczos_many(lam_hip_ctx *ctx, int nprobes, const void *z_host, uint64_t seed, int steps, lam_hip_stats *stats,
+                         int32_t *steps_run, double *znorm2, double *alpha, double *beta);
+/* What the last lam_hip_lanczos_many left, for its first nprobes probes: *steps (the row length of alpha and beta), steps_run, znorm2,
+ * alpha and beta as that call lays them out; any pointer may be NULL.  More probes than were run: LAM_HIP_EINVAL; no coefficients:
+ * LAM_HIP_ESTATE. */
+int lam_hip_get_lanczos_many(lam_hip_ctx *ctx, int nprobes, int32_t *steps, int32_t *steps_run, double *znorm2, double *alpha,
+                             double *beta);
+/* Host arithmetic on the coefficients of the last lam_hip_lanczos_many, for nshifts <= LAM_HIP_MAX_SHIFTS shifts (sigma == NULL with
+ * nshifts == 1: no shift):  q_{s,j} = znorm2_j * lam_hip_tridiag_quadrature(T_j over its steps_run_j, sigma_s);  estimate[s] = the
+ * mean over the probes, summed in ascending j;  std_error[s] = the sample standard deviation (ddof 1) / sqrt(nprobes), NaN for one
+ * probe;  per_probe[s * nprobes + j] = q_{s,j} (may be NULL, as may the other two).  For Rademacher probes estimate[s] estimates
+ * tr f(A + sigma_s I); with LAM_HIP_QUAD_LOG that is log det(A + sigma_s I).  A node the function cannot take is LAM_HIP_EINVAL
+ * naming the probe, the shift and the node; so are a probe with a non-finite coefficient, an unknown fn, a bad param. */
+int lam_hip_trace_quadrature(lam_hip_ctx *ctx, int fn, double param, int nshifts, const double *sigma, double *estimate,
+                             double *std_error, double *per_probe);
+/* Host-only and context-free, like lam_hip_tridiag_eigen, on which it stands (csrc/lam_host_quad.h): for the symmetric tridiagonal T
+ * with diagonal alpha[0 .. k) and off-diagonal beta[0 .. k-1),  out[s] = e_1^T f(T + sigma_s I) e_1 = sum_i S_{1i}^2 f(theta_i +
+ * sigma_s), i ascending in theta.  The eigenproblem is solved once, on the reversed tridiagonal, so that the one-row QL sweep
+ * carries the FIRST components: O(k^2), S is never formed, and each shift is one pass over the k nodes.  sigma == NULL with
+ * nshifts == 1 means no shift.  LAM_HIP_EINVAL: k outside 1..LAM_HIP_MAX_LANCZOS, nshifts < 1, a NULL array, an unknown fn; a
+ * non-finite coefficient or shift; under LAM_HIP_QUAD_POW a param that is not an integer >= 0; a node theta_i + sigma_s that is <= 0
+ * under LAM_HIP_QUAD_LOG, == 0 under LAM_HIP_QUAD_INV, or not finite -- then bad[0] / bad[1] (bad may be NULL) hold the first such
+ * shift and node, as lam_hip_chol_inverse reports bad_col, and -1 / -1 otherwise.  lam_hip_last_error(NULL) has the words. */
+int lam_hip_tridiag_quadrature(int k, const double *alpha, const double *beta, int fn, double param, int nshifts,
+                               const double *sigma, double *out, int *bad);
 
 /* ---- deflated CG for the batch ----------------------------------------------------------------
  * CG whose residuals stay orthogonal to a small subspace W (Nicolaides; Saad, Yeung, Erhel, Guyomarc'h, SISC 2000): it converges as
