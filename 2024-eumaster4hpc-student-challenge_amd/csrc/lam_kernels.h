@@ -876,9 +876,16 @@ pack_rows_kernel(const double *__restrict__ A, uint64_t lda, uint64_t ncols, uin
 // tile order, s_p staging, lane-to-column mapping and fma sequence per lane (the +0 terms of a ragged tile included), the same
 // wave_sum, s_part order, store_y and publish_partial -- so the result is bit for bit the plain kernel's.  What differs is where an
 // element comes from: four coalesced non-temporal loads give a lane its 8 elements of a row and tile, the tile's exception values
-// are staged into LDS next to the p tile behind the same barrier (the first 64 of a list with the tile's other loads, the rest
-// of a longer list once the header has told its length), and every element is one LDS read of its (row, tile)'s list -- an exception's value, or the reserved +0.0 at one address for
-// the rest of the wave -- and a select: no branch per element.
+// are staged into LDS next to the p tile behind the same barrier, and every element is one LDS read of its (row, tile)'s list --
+// an exception's value, or the reserved +0.0 at one address for the rest of the wave -- and a select.  (The source has no branch
+// per element; the compiler emits each select as a two-sided exec-mask region, the decode under one mask and the list read under
+// the other: 16 such regions a tile and lane.)
+// A tile, in order: (1) the element loads, the two headers and the first 64 values of the two lists are issued -- they depend on
+// nothing the workgroup shares; (2) first barrier: every wave has finished the previous tile's reads of s_p and s_exc; (3) the
+// p tile's four loads a thread, back to back, ONE wait (vmcnt(0): it also covers what (1) issued), four LDS writes; the lists'
+// first values are written, the rest of a list longer than 64 is loaded and written (one more round trip, long lists only);
+// (4) second barrier; (5) the FMAs.  Between the two barriers lies one L2 round trip for p, which runs under the HBM latency of
+// the elements.  DESIGN section 18 has the variants that were measured against this one and lost.
 // One whole column segment [0, seg_end[0]) only (the launcher sends panels to the plain kernel).
 template <bool NT>
 __global__ void __launch_bounds__(512)
@@ -955,14 +962,22 @@ gemv_packed_kernel(GemvArgs<double, double> a, PackedMat pk)
         if (stager) first = pk.exc[(unit0[wave - 1] + tt) * kPackCap + lane];
         __syncthreads();
         {
+            // the p tile: four 16-byte loads a thread, issued back to back and written when all have come -- one round trip between
+            // the tile's two barriers, not four (a rolled loop waits vmcnt(0) for each load in turn, and with it for every element,
+            // header and list load issued in front of the first barrier).  Pairs behind the segment's end are loaded from a
+            // 16-byte zero: the zeros the lanes past the end of a ragged tile multiply with (cols is even: the packed product
+            // runs on whole 16-byte vectors only)
             typedef double pvec_t __attribute__((ext_vector_type(2)));
-            const pvec_t *src = reinterpret_cast<const pvec_t *>(a.p + c0);
+            typedef const __attribute__((address_space(1))) pvec_t *gptr_t;
             pvec_t *dst = reinterpret_cast<pvec_t *>(s_p);
-            const uint32_t nv = cols / 2;
-            for (uint32_t i = tid; i < nv; i += NTHREADS) dst[i] = src[i];
-            for (uint32_t i = nv * 2 + tid; i < cols; i += NTHREADS) s_p[i] = a.p[c0 + i];
-            for (uint32_t i = cols + tid; i < (uint32_t)TILE && i < (cols + STEP * WAVES - 1) / (STEP * WAVES) * (STEP * WAVES); i += NTHREADS)
-                s_p[i] = 0.0;
+            pvec_t v[TILE / 2 / NTHREADS];
+#pragma unroll
+            for (int k = 0; k < TILE / 2 / NTHREADS; k++) {
+                const uint32_t col = 2u * ((uint32_t)tid + (uint32_t)k * NTHREADS);
+                v[k] = *(col < cols ? (gptr_t)(a.p + c0 + col) : (gptr_t)kZeroVec16);      // global loads, not flat ones
+            }
+#pragma unroll
+            for (int k = 0; k < TILE / 2 / NTHREADS; k++) dst[tid + k * NTHREADS] = v[k];
         }
         uint32_t shift[R];
 #pragma unroll
