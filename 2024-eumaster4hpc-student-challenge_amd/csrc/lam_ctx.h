@@ -216,7 +216,8 @@ struct PcgState {
     double badk_value = 0.0;
 };
 
-// Packed fp64 image of the matrix (option "packed", lam_host_pack.h): what gemv_packed_kernel reads in place of A.  One allocation,
+// Packed fp64 image of the matrix (options "packed" and "packed_many", lam_host_pack.h): what gemv_packed_kernel and
+// multi_gemv_packed_kernel read in place of A.  One allocation,
 // grow-only, kept for the life of the context (a large hipFree slows whatever runs next); its content follows
 // lam_hip_ctx::matrix_gen, as sym_checked_gen and PcgState::diag_gen do.  A stays where it is: every other path reads it as before.
 // Auto packs once a content has served kPackAfter plain products: the measured break-even, pack time / (plain - packed product time),
@@ -232,7 +233,7 @@ struct PackState {
     uint64_t ready_gen = ~0ull;          // matrix_gen the image holds
     uint64_t refused_gen = ~0ull;        // matrix_gen that is not packable (a tile overflowed) or found no memory: not tried again
     uint64_t count_gen = ~0ull;          // matrix_gen `plain` counts for
-    uint64_t plain = 0;                  // plain products of the eligible shape since the content changed
+    uint64_t plain = 0;                  // plain products of an eligible shape, single or batched (K <= 4), since the content changed
     uint64_t exc_total = 0;              // exception-list values a product reads of the whole image (8 bytes each)
     double pack_s = 0.0;                 // seconds the last pack took (host clock around the pass)
 };
@@ -246,6 +247,9 @@ struct lam_hip_ctx {
     int64_t opt_packed = -1;       // fp64 general product on the packed image: -1 auto, 0 never, 1 pack in front of the next product
     int64_t opt_packed_after = kPackAfter;                  // testing: auto's two thresholds (plain products served, bytes of matrix),
     int64_t opt_packed_min_bytes = (int64_t)kPackMinBytes;  // so that the switch runs at sizes a test can afford
+    int64_t opt_packed_many = -1;  // the batched product (fp64, K <= 4) on the packed image: -1 auto (the admitted K, under "packed"'s
+                                   // thresholds), 0 never, 1 pack in front of the next batched product and read the image at every K <= 4
+    bool packed_many_effective = false;   // the last batched product launch read the image
     int dtype = LAM_HIP_F64;
     int total_shards = 1;          // P
     int rank = 0, nranks = 1;      // rank mode (one local shard == shard `rank`)
@@ -351,7 +355,11 @@ struct lam_hip_ctx {
         return opt_packed != 0 && dtype == LAM_HIP_F64 && !rank_mode && total_shards == 1 && opt_symmetric == 0 && opt_generic == 0 &&
                opt_gemv_variant < 0 && n > 0;
     }
-    bool pack_active() const { return pack_eligible() && pack.buf != nullptr && pack.ready_gen == matrix_gen; }
+    // the image belongs to the matrix content: either reader (the single product, the batched one) may have caused it to be built
+    bool pack_image_ready() const { return pack.buf != nullptr && pack.ready_gen == matrix_gen; }
+    bool pack_active() const { return pack_eligible() && pack_image_ready(); }
+    // option "packed_many": the batch's own scope (fp64, one shard), independent of "packed"
+    bool pack_many_eligible() const { return opt_packed_many != 0 && dtype == LAM_HIP_F64 && !rank_mode && total_shards == 1 && n > 0; }
     // a shard's record in the symmetric product's gather: its full-length contribution, then (8-byte aligned) its part of p.Ap
     uint64_t symv_stride_bytes() const { return (n * esz_v() + 7) / 8 * 8 + 8; }
 

@@ -92,6 +92,7 @@ int deflate_build(lam_hip_ctx *c, const char *fn, int mm, const void *src, hipMe
     for (int first = 0; first < mm; first += group) {
         const int count = std::min(group, mm - first), K = multi_k_for(count);
         m.last_K = K;
+        LAMCHK(pack_many_maybe(c, K));
         LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
             using I = decltype(impl);
             using TA = typename ImplTraits<I>::TA;

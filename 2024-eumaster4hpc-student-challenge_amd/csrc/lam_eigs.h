@@ -156,6 +156,7 @@ int lam_hip_eigs(lam_hip_ctx *c, int which, int nev, int max_steps, double tol, 
             const int chunk = std::min(check_every, max_steps - steps);
             for (int q = 1; q <= chunk; q++) {
                 const int step = steps + q, k = step - 1, slot = k % kLag, mm = k + 1;
+                LAMCHK(pack_many_maybe(c, 1));          // option "packed_many": in front of the product step, outside its event pair
                 const double te = now_s();
                 if (m.timed_slot[slot]) {
                     HIPCHK(c, hipEventSynchronize(m.ev1[slot]));
@@ -301,6 +302,7 @@ int lam_hip_eig_residuals(lam_hip_ctx *c, int nev, double *res)
         LanczosTheta th;
         for (int j = 0; j < kMaxRhs; j++) th.t[j] = j < count ? z.theta[first + j] : 0.0;
         double out[kMaxRhs];
+        LAMCHK(pack_many_maybe(c, K));
         LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
             using I = decltype(impl);
             using TA = typename ImplTraits<I>::TA;

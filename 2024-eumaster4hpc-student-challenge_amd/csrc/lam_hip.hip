@@ -1100,6 +1100,13 @@ int lam_hip_set_option(lam_hip_ctx *c, const char *name, int64_t value)
             return fail(c, LAM_HIP_EINVAL, "packed = %lld: -1 (automatic), 0 (never) or 1 (pack in front of the next product)", (long long)value);
         c->opt_packed = value;
     }
+    else if (!strcmp(name, "packed_many")) {
+        // the batched product's own switch, independent of "packed"
+        if (value < -1 || value > 1)
+            return fail(c, LAM_HIP_EINVAL, "packed_many = %lld: -1 (automatic), 0 (never) or 1 (pack in front of the next batched product, K <= 4)",
+                        (long long)value);
+        c->opt_packed_many = value;
+    }
     else if (!strcmp(name, "packed_after") || !strcmp(name, "packed_min_bytes")) {
         if (value < 0) return fail(c, LAM_HIP_EINVAL, "%s = %lld: a count / a number of bytes, not negative", name, (long long)value);
         (!strcmp(name, "packed_after") ? c->opt_packed_after : c->opt_packed_min_bytes) = value;
@@ -1156,6 +1163,8 @@ int lam_hip_get_option(const lam_hip_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "symmetric")) *value = c->opt_symmetric;
     else if (!strcmp(name, "symmetric_many")) *value = c->opt_symmetric_many;
     else if (!strcmp(name, "packed")) *value = c->opt_packed;
+    else if (!strcmp(name, "packed_many")) *value = c->opt_packed_many;
+    else if (!strcmp(name, "packed_many_effective")) *value = c->packed_many_effective ? 1 : 0;
     else if (!strcmp(name, "packed_after")) *value = c->opt_packed_after;
     else if (!strcmp(name, "packed_min_bytes")) *value = c->opt_packed_min_bytes;
     else if (!strcmp(name, "packed_effective")) *value = c->pack_active() ? 1 : 0;

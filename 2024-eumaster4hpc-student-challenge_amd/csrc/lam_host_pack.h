@@ -52,6 +52,19 @@ LAM_HOST_DEVICE void pack_pos(uint32_t j, uint32_t *w, uint32_t *l, uint32_t *e)
     *l = (j & 127u) >> 1;
     *e = 2u * (j >> 10) + (j & 1u);
 }
+// The batched product's traversal of the image (multi_gemv_packed_kernel, fp64, K = 1, 2, 4 columns): its batch tile holds
+// kPackTile / K columns, kPackManySteps / K steps of 512 (4 waves x 64 lanes x 2 columns).  Wave w of step s of batch tile tt
+// covers the 128 global columns behind (tt * (8 / K) + s) * 512 + w * 128: lane l's two are elements 2 * pair, 2 * pair + 1 of lane
+// l of wave group `group` of (row, tile) unit `unit` -- wave w reads groups w and w + 4 in turn, one pair every second step.
+constexpr uint32_t kPackManySteps = 8;         // steps of the batched product in a unit
+constexpr uint32_t kPackManyMaxK = 4;
+LAM_HOST_DEVICE void pack_many_pos(uint32_t K, uint32_t tt, uint32_t s, uint32_t w, uint32_t *unit, uint32_t *group, uint32_t *pair)
+{
+    const uint32_t q = tt * (kPackManySteps / K) + s;
+    *unit = q / kPackManySteps;
+    *group = w + 4u * (q & 1u);
+    *pair = (q % kPackManySteps) >> 1;
+}
 // byte offsets inside a wave group
 LAM_HOST_DEVICE uint32_t pack_off_lo(uint32_t l, uint32_t e) { return (e >> 2) * 1024u + l * 16u + (e & 3u) * 4u; }
 LAM_HOST_DEVICE uint32_t pack_off_mid(uint32_t l, uint32_t e) { return 2048u + l * 16u + e * 2u; }

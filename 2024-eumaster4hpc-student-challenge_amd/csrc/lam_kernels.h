@@ -2504,6 +2504,206 @@ multi_gemv_kernel(MultiGemvArgs<TA, TV> a)
     }
 }
 
+// The body of multi_gemv_kernel<double, double, K, 4, 4, NT, SHIFT> on the packed image (option "packed_many", K = 1, 2, 4): the same
+// grid, the same rotated order of the batch tiles, p staging target, lane-to-column mapping and fma sequence per accumulator (the +0
+// terms of a ragged tile included), the same wave_sum, s_part order, SHIFT fma, store of y and partials -- the result is bit for bit
+// the plain kernel's.  What differs is where an element comes from (gemv_packed_kernel's decode: one LDS read of the (row, unit)'s
+// list per element and a select).
+// A unit of the image (one row x 4096 columns) spans K batch tiles, and thread (wave, lane) reads lane `lane` of its wave groups
+// wave and wave + 4 (pack_many_pos).  The batch tiles of the rotated order are therefore walked as VISITS of a unit: the consecutive
+// batch tiles [sub_lo, sub_hi) that share it.  At the start of a visit the thread loads its 2 x 56 bytes of each of the 4 rows, the
+// 4 headers and the first 64 values of the 4 lists, all in front of the visit's first barrier, and keeps elements, header and list
+// for every batch tile of the visit; the rotation can start inside a unit (K = 2, 4), which then gets a first and a last visit, and
+// a partial visit skips the low-word vectors none of its batch tiles reads.  A batch tile, as in the plain kernel: barrier, the p
+// tile (eight 16-byte loads a thread back to back, one wait, eight LDS writes; the lists behind the first barrier of a visit),
+// barrier, the FMAs.
+template <int K, bool NT, bool SHIFT>
+__global__ void __launch_bounds__(256)
+multi_gemv_packed_kernel(MultiGemvArgs<double, double> a, PackedMat pk)
+{
+    constexpr int R = 4, WAVES = 4, NTHREADS = WAVES * 64, SUPER = 128 * WAVES;
+    constexpr int TILE = multi_tile<double, double, K, WAVES>();
+    constexpr int SPT = TILE / SUPER;                   // steps of a batch tile
+    static_assert(K == 1 || K == 2 || K == 4, "a unit of the image is a whole number of batch tiles");
+    static_assert(TILE * K == (int)kPackTile && SPT * K == (int)kPackManySteps, "K batch tiles are one unit");
+    static_assert(R == WAVES, "wave r stages the first values of row r's list");
+    typedef double pvec_t __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(1))) pvec_t *gptr_t;
+    constexpr int NPL = TILE * K / 2 / NTHREADS;        // 16-byte vectors of the p tile a thread stages
+
+    __shared__ __attribute__((aligned(16))) double s_p[TILE * K];
+    __shared__ double s_exc[R][kPackCap + 1];
+    double (*s_part)[WAVES] = reinterpret_cast<double (*)[WAVES]>(s_p);
+    double *s_dot = s_p + R * K * WAVES;
+
+    if (a.sc != nullptr && a.sc->all_stop) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint64_t row_first = (uint64_t)blockIdx.x * R;
+    const uint32_t woff = (uint32_t)wave * 128u + (uint32_t)lane * 2u;
+
+    const uint32_t nunits = pk.ntiles;
+    uint64_t unit0[R];                                  // the row's first unit
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        uint64_t row = row_first + r;
+        if (row >= a.nrows) row = a.nrows - 1;
+        unit0[r] = row * nunits;
+    }
+    uint64_t unit0_mine = unit0[0];                     // of the row whose list this wave stages
+#pragma unroll
+    for (int r = 1; r < R; r++) if (wave == r) unit0_mine = unit0[r];
+    double acc[R][K];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int j = 0; j < K; j++) acc[r][j] = 0.0;
+    if (tid < R) s_exc[tid][kPackZeroIdx] = 0.0;        // the reserved index; never overwritten (visible behind the first barrier)
+
+    uint32_t perlane = 0;                               // zero, but not to the compiler (gemv_packed_kernel: the headers stay per lane)
+    asm volatile("" : "+v"(perlane));
+
+    const uint32_t ntiles = (uint32_t)((a.ncols + TILE - 1) / TILE);
+    const uint32_t tt0 = blockIdx.x % ntiles;
+    const uint32_t sub0 = tt0 % (uint32_t)K;
+    const uint32_t nvisits = nunits + (sub0 != 0 ? 1u : 0u);
+    uint32_t u = tt0 / (uint32_t)K;
+    for (uint32_t v = 0; v < nvisits; v++) {
+        const uint32_t left = ntiles - u * (uint32_t)K;             // batch tiles of unit u (the last unit may hold fewer than K)
+        const uint32_t sub_lo = v == 0 ? sub0 : 0u;
+        const uint32_t sub_hi = v == nunits ? sub0 : (left < (uint32_t)K ? left : (uint32_t)K);
+        // low words 0..3 of a lane and group are pairs 0 and 1 (the first half of the unit's batch tiles), 4..7 pairs 2 and 3
+        const bool need0 = K == 1 || sub_lo < (uint32_t)K / 2, need1 = K == 1 || sub_hi > (uint32_t)K / 2;
+        pack_u4 lo0[R][2], lo1[R][2], mid[R][2];
+        pack_u2 hi[R][2];
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const unsigned char *g = pk.data + ((unit0[r] + u) * kPackGroups + (uint64_t)(wave + 4 * h)) * kPackGroupBytes;
+                const pack_u4 *q0 = reinterpret_cast<const pack_u4 *>(g + pack_off_lo(lane, 0));
+                const pack_u4 *q1 = reinterpret_cast<const pack_u4 *>(g + pack_off_lo(lane, 4));
+                const pack_u4 *qm = reinterpret_cast<const pack_u4 *>(g + pack_off_mid(lane, 0));
+                const pack_u2 *qh = reinterpret_cast<const pack_u2 *>(g + pack_off_hi(lane, 0));
+                lo0[r][h] = 0u;
+                lo1[r][h] = 0u;
+                if (need0) lo0[r][h] = NT ? __builtin_nontemporal_load(q0) : *q0;
+                if (need1) lo1[r][h] = NT ? __builtin_nontemporal_load(q1) : *q1;
+                mid[r][h] = NT ? __builtin_nontemporal_load(qm) : *qm;
+                hi[r][h] = NT ? __builtin_nontemporal_load(qh) : *qh;
+            }
+        uint32_t head[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) head[r] = pk.hdr[unit0[r] + u + perlane];
+        const double first = pk.exc[(unit0_mine + u) * kPackCap + lane];
+        uint32_t shift[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) shift[r] = 0u;
+#pragma unroll
+        for (int sub = 0; sub < K; sub++) {
+            if ((uint32_t)sub < sub_lo || (uint32_t)sub >= sub_hi) continue;
+            const uint64_t c0 = (uint64_t)(u * (uint32_t)K + (uint32_t)sub) * TILE;
+            const uint32_t cols = (uint32_t)((a.ncols - c0 < (uint64_t)TILE) ? (a.ncols - c0) : (uint64_t)TILE);
+            __syncthreads();
+            {
+                // cols is even, so cols * K elements are whole 16-byte vectors; behind them zeros, as the plain kernel stages them
+                // (it stops at the next whole step; the rest of the tile is not read)
+                const double *src = a.p + c0 * K;
+                pvec_t *dst = reinterpret_cast<pvec_t *>(s_p);
+                const uint32_t nv = cols * K / 2;
+                pvec_t pv[NPL];
+#pragma unroll
+                for (int k = 0; k < NPL; k++) {
+                    const uint32_t i = (uint32_t)tid + (uint32_t)k * NTHREADS;
+                    pv[k] = *(i < nv ? (gptr_t)(src + 2 * (size_t)i) : (gptr_t)kZeroVec16);
+                }
+#pragma unroll
+                for (int k = 0; k < NPL; k++) dst[tid + k * NTHREADS] = pv[k];
+            }
+            if ((uint32_t)sub == sub_lo) {
+                s_exc[wave][lane] = first;
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    shift[r] = pack_exp_shift(pack_header_base(head[r]));
+                    const uint32_t cnt = min(pack_header_count(head[r]), kPackCap);
+                    const double *e = pk.exc + (unit0[r] + u) * kPackCap;
+                    for (uint32_t i = kPackFirst + tid; i < cnt; i += NTHREADS) s_exc[r][i] = e[i];     // a long list: one more round trip
+                }
+            }
+            __syncthreads();
+            const int nsteps = (int)((cols + SUPER - 1) / SUPER);
+#pragma unroll
+            for (int s = 0; s < SPT; s++) {
+                if (s < nsteps) {
+                    uint32_t unit_rel, group, pair;
+                    pack_many_pos((uint32_t)K, (uint32_t)sub, (uint32_t)s, 0u, &unit_rel, &group, &pair);      // unit_rel == 0
+                    const int h = (int)(group >> 2);
+                    pvec_t pq[K];
+                    const pvec_t *lp = reinterpret_cast<const pvec_t *>(s_p + (size_t)((uint32_t)s * SUPER + woff) * K);
+#pragma unroll
+                    for (int q = 0; q < K; q++) pq[q] = lp[q];
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const int e = 2 * (int)pair + i;
+                        double av[R];
+#pragma unroll
+                        for (int r = 0; r < R; r++) {
+                            const uint32_t l = e < 4 ? lo0[r][h][e & 3] : lo1[r][h][e & 3];
+                            const uint32_t w = ((hi[r][h][e >> 2] >> (8 * (e & 3))) & 0xffu) << 16 | ((mid[r][h][e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                            const bool x = pack_is_exception(w);
+                            const double ev = s_exc[r][x ? min(l, kPackZeroIdx) : kPackZeroIdx];
+                            av[r] = x ? ev : __longlong_as_double((long long)pack_decode(l, w, shift[r]));
+                        }
+#pragma unroll
+                        for (int j = 0; j < K; j++) {
+                            const double pij = pq[(i * K + j) / 2][(i * K + j) % 2];
+#pragma unroll
+                            for (int r = 0; r < R; r++) acc[r][j] = fma_tv(av[r], pij, acc[r][j]);
+                        }
+                    }
+                }
+            }
+        }
+        u = (u + 1 == nunits) ? 0 : u + 1;
+    }
+
+    __syncthreads();                                    // the last tile has been consumed: s_p becomes the reduction scratch
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            double s = wave_sum(acc[r][j]);
+            if (lane == 0) s_part[r * K + j][wave] = s;
+        }
+    __syncthreads();
+    if (tid < R * K) {
+        const int r = tid / K, j = tid % K;
+        const uint64_t row = row_first + r;
+        double d = 0.0;
+        if (row < a.nrows) {
+            double s = s_part[tid][0];
+#pragma unroll
+            for (int w = 1; w < WAVES; w++) s += s_part[tid][w];
+            const double pj = a.p[row * K + j];
+            if constexpr (SHIFT) s = fma_tv(a.shift[j], pj, s);
+            a.y[row * K + j] = s;
+            d = s * pj;
+        }
+        s_dot[tid] = d;
+    }
+    if (a.partial != nullptr) {
+        __syncthreads();
+        if (tid < K) {
+            double t = s_dot[tid];
+#pragma unroll
+            for (int r = 1; r < R; r++) t += s_dot[r * K + tid];
+            a.partial[(size_t)tid * gridDim.x + blockIdx.x] = t;
+        }
+    }
+}
+
 // Symmetric batched product (option "symmetric_many", lam_multi.h multi_launch_gemv): Y = A P for K = 1, 2, 4 interleaved columns
 // reading every pair {A_ij, A_ji} once -- the two passes of the single symmetric product ("Symmetric product" above: one shard, the
 // upper triangle, the plan of symv_plan unchanged) with K of everything a lane keeps per column of P: its p values, its column

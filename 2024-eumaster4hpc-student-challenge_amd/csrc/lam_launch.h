@@ -18,6 +18,8 @@ Finalize no_finalize(const lam_hip_ctx *c)
     return f;
 }
 
+void pack_count_plain(lam_hip_ctx *c);      // below, with the rest of the packed image's host side
+
 // ---- typed implementation ----------------------------------------------------------------------
 // (the symmetric product's plan -- SymvPlan, symv_plan -- is host-only arithmetic: lam_host_plan.h)
 template <typename TA, typename TV>
@@ -202,8 +204,7 @@ struct Impl {
                     LAUNCHED(c);
                     return 0;
                 }
-                if (pk.count_gen != c->matrix_gen) { pk.count_gen = c->matrix_gen; pk.plain = 0; }
-                pk.plain++;
+                pack_count_plain(c);
             }
         }
         if (fast_ok(c)) {
@@ -230,23 +231,32 @@ struct Impl {
     }
 };
 
-// Option "packed": build the packed image of the current matrix content in front of the next product when it is due -- value 1: now;
-// auto: once the content has served kPackAfter plain products, the matrix has at least kPackMinBytes (testing options "packed_after" /
-// "packed_min_bytes" move the two) and the device reports twice the image free.  One pass of pack_rows_kernel on the shard's stream, outside every timing event pair (its callers sit in front of
-// the product step).  Never an error of its own: no memory, or a (row, tile) with more than kPackCap exceptions, and the plain
-// kernel goes on running for this content.
+// The packed image belongs to the matrix content; either of its readers may cause it to be built (pack_maybe below for the single
+// product, pack_many_maybe in lam_multi.h for the batched one), and both read whatever image holds the current matrix_gen.
+// pack_auto_due: automatic mode's two thresholds, shared by the readers -- the content has served "packed_after" plain products (kPackAfter;
+// single and batched ones of an eligible shape count on the one counter, pack_count_plain) and the matrix has "packed_min_bytes" (kPackMinBytes).
+// pack_build: the image of the current content -- allocation (grow-only; automatic mode wants twice the image free), one pass of
+// pack_rows_kernel on the shard's stream, outside every timing event pair (the callers sit in front of the product step), the
+// refusal bookkeeping.  Never an error of its own: no memory, or a (row, tile) with more than kPackCap exceptions, and the plain
+// kernels go on running for this content.
 int set_dev(lam_hip_ctx *c, const ShardBase &s);
-int pack_maybe(lam_hip_ctx *c)
+bool pack_auto_due(const lam_hip_ctx *c)
 {
-    if (!c->pack_eligible() || !c->have_matrix) return 0;
+    const PackState &pk = c->pack;
+    if (pk.count_gen != c->matrix_gen || pk.plain < (uint64_t)c->opt_packed_after) return false;
+    return c->sh[0].nrows * c->lda * 8ull >= (uint64_t)c->opt_packed_min_bytes;
+}
+void pack_count_plain(lam_hip_ctx *c)
+{
+    PackState &pk = c->pack;
+    if (pk.count_gen != c->matrix_gen) { pk.count_gen = c->matrix_gen; pk.plain = 0; }
+    pk.plain++;
+}
+int pack_build(lam_hip_ctx *c, bool automatic)
+{
     PackState &pk = c->pack;
     if (pk.ready_gen == c->matrix_gen || pk.refused_gen == c->matrix_gen) return 0;
     ShardBase &s = c->sh[0];
-    const bool automatic = c->opt_packed < 0;
-    if (automatic) {
-        if (pk.count_gen != c->matrix_gen || pk.plain < (uint64_t)c->opt_packed_after) return 0;
-        if (s.nrows * c->lda * 8ull < (uint64_t)c->opt_packed_min_bytes) return 0;
-    }
     const uint64_t ncols = c->ncols_vec();
     const uint64_t ntiles = (ncols + kPackTile - 1) / kPackTile;
     const PackLayout L = pack_layout(s.nrows, ntiles);
@@ -285,6 +295,15 @@ int pack_maybe(lam_hip_ctx *c)
     pk.exc_total = got[1];
     pk.ready_gen = c->matrix_gen;
     return 0;
+}
+
+// Option "packed": who is due for the single product -- value 1: now; auto: pack_auto_due
+int pack_maybe(lam_hip_ctx *c)
+{
+    if (!c->pack_eligible() || !c->have_matrix) return 0;
+    const bool automatic = c->opt_packed < 0;
+    if (automatic && !pack_auto_due(c)) return 0;
+    return pack_build(c, automatic);
 }
 
 // bytes one product of the shard reads: the plain kernel's, or the packed image's elements, headers and exception-list values

@@ -26,6 +26,8 @@
 // Only MINRES takes a negative shift and can leave one in force; CG refuses to run under it.
 // Option "symmetric_many" (K <= 4): the product launch becomes the two passes of the symmetric batched product (multi_sym_launch: every
 // pair {A_ij, A_ji} read once, one more launch per product, its own plan and partials in MultiState); K = 8 and option 0 are untouched.
+// Option "packed_many" (fp64, K <= 4, where "symmetric_many" does not engage): the product launch reads the packed image of the matrix
+// (multi_gemv_packed_kernel: the same grid, partials and bits); pack_many_maybe, in front of a product, is who causes it to be built.
 #pragma once
 
 static_assert(lam::kMaxRhs == LAM_HIP_MAX_RHS, "include/lam_hip.h states the limit");
@@ -257,6 +259,39 @@ int multi_sym_grid(const lam_hip_ctx *c) { return (int)((c->n + kSymvReduceRows 
 // p.Ap partials per column of the product multi_launch_gemv runs for instantiation K: what its consumers are told
 int multi_product_blocks(const lam_hip_ctx *c, int K) { return multi_sym_wanted(c, K) ? multi_sym_grid(c) : multi_gemv_grid(c); }
 
+// ---- packed batched product (option "packed_many"; kernel: lam_kernels.h, multi_gemv_packed_kernel) --------------------------
+// Automatic mode (-1) admits the K whose packed product measured faster than the plain one of the same build and process by more than
+// the spread between the windows of the two figures (multi_sym_admitted's rule; tools/packed_many_probe.py,
+// profiles/packed_many_probe.txt; packed / plain per product of lam_hip_gemv_many_only, fp64):
+//   N = 65536  K = 1: 0.898 (4.365 / 4.863 ms, spread 0.007)   K = 2: 0.964 (5.062 / 5.252, spread 0.010)   K = 4: 1.105 (5.959 / 5.393)
+//   N = 32768  K = 1: 0.897 (1.095 / 1.220 ms, spread 0.001)   K = 2: 1.040 (1.287 / 1.237)                  K = 4: 1.119 (1.553 / 1.387)
+// K = 1 wins at both sizes and is admitted: the single packed product's ratio carries over whole.  K = 2 wins at N = 65536 only and
+// K = 4 loses at both (a visit of a unit holds 112 element registers a thread: two workgroups a CU, and K pairs of barriers with
+// nothing in flight between them); they read false here and stay reachable through value 1.
+// Break-even of K = 1, pack time / (plain - packed): 16.3 ms / 0.498 ms = 32.7 products at N = 65536, 31.7 at N = 32768 -- half the
+// single product's 64.4, because the batch's plain kernel is the slower one.  The one threshold (kPackAfter = 65) stays: it is
+// shared with the single product, and a context that packs after 65 products instead of 33 gives away 16 ms once.
+bool pack_many_admitted(int K)
+{
+    static constexpr bool admitted[kPackManyMaxK + 1] = {/* K = - 1 2 - 4 */ false, true, false, false, false};
+    return K >= 1 && K <= (int)kPackManyMaxK && admitted[K];
+}
+// does the batched product of instantiation K read the image, given one of the current content?
+bool pack_many_reads(const lam_hip_ctx *c, int K)
+{
+    if (!c->pack_many_eligible() || K > (int)kPackManyMaxK || multi_sym_wanted(c, K) || !c->pack_image_ready()) return false;
+    return c->opt_packed_many == 1 || pack_many_admitted(K);
+}
+// The batch's trigger, where pack_maybe is the single product's: in front of a batched product of instantiation K, outside every
+// timing event pair.  Value 1: the image is built now; automatic: for an admitted K once "packed"'s thresholds hold (pack_auto_due).
+int pack_many_maybe(lam_hip_ctx *c, int K)
+{
+    if (!c->pack_many_eligible() || !c->have_matrix || K > (int)kPackManyMaxK || multi_sym_wanted(c, K)) return 0;
+    const bool automatic = c->opt_packed_many < 0;
+    if (automatic && (!pack_many_admitted(K) || !pack_auto_due(c))) return 0;
+    return pack_build(c, automatic);
+}
+
 void multi_sym_release(MultiState &m)
 {
     symv_dev_release(m.sym);
@@ -315,10 +350,13 @@ int multi_sym_launch(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const 
 // one there was), else the K shifts of the batch (MultiState::shift): Y_j = (A + s_j I) P_j
 // Under option "symmetric_many" (K <= 4) the launch site runs the two passes of the symmetric batched product instead
 // (multi_sym_launch): one more launch, and ceil(n / 32) partials per column instead of multi_gemv_grid(c) -- multi_product_blocks.
+// Under option "packed_many" (fp64, K <= 4, the symmetric batched product not wanted: that one reads half the bytes and wins) and an
+// image of the current content, multi_gemv_packed_kernel runs in place of multi_gemv_kernel: the same grid, partials and bits.
 template <typename TA, typename TV, int K>
 int multi_launch_gemv(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const MultiScalars *sc, const double *shift = nullptr)
 {
     ShardBase &s = c->sh[0];
+    c->packed_many_effective = false;
     if constexpr (K <= kSymvManyMaxK)
         if (multi_sym_wanted(c, K)) return multi_sym_launch<TA, TV, K>(c, P, Y, partial, sc, shift);
     c->symv_many_effective = false;
@@ -326,6 +364,31 @@ int multi_launch_gemv(lam_hip_ctx *c, const TV *P, TV *Y, double *partial, const
     a.A = (const TA *)s.A; a.p = P; a.y = Y; a.partial = partial; a.sc = sc;
     a.nrows = c->n; a.ncols = c->ncols_vec(); a.lda = c->lda;
     for (int j = 0; j < kMaxRhs; j++) a.shift[j] = shift ? (TV)shift[j] : (TV)0;
+    if constexpr (std::is_same<TA, double>::value && K <= (int)kPackManyMaxK) {
+        if (c->pack_many_eligible()) {
+            const PackState &pk = c->pack;
+            if (pack_many_reads(c, K) && c->n == pk.nrows) {
+                const PackLayout L = pack_layout(pk.nrows, pk.ntiles);
+                PackedMat m;
+                m.data = (const unsigned char *)pk.buf + L.data;
+                m.exc = (const double *)((const char *)pk.buf + L.exc);
+                m.hdr = (const uint32_t *)((const char *)pk.buf + L.hdr);
+                m.ntiles = (uint32_t)pk.ntiles;
+                const dim3 grid(multi_gemv_grid(c)), block(kMultiWaves * 64);
+                if (shift) {
+                    if (c->opt_nt) hipLaunchKernelGGL((multi_gemv_packed_kernel<K, true, true>), grid, block, 0, s.stream, a, m);
+                    else hipLaunchKernelGGL((multi_gemv_packed_kernel<K, false, true>), grid, block, 0, s.stream, a, m);
+                } else {
+                    if (c->opt_nt) hipLaunchKernelGGL((multi_gemv_packed_kernel<K, true, false>), grid, block, 0, s.stream, a, m);
+                    else hipLaunchKernelGGL((multi_gemv_packed_kernel<K, false, false>), grid, block, 0, s.stream, a, m);
+                }
+                LAUNCHED(c);
+                c->packed_many_effective = true;
+                return 0;
+            }
+            pack_count_plain(c);
+        }
+    }
     if (shift)
         hipLaunchKernelGGL((multi_gemv_kernel<TA, TV, K, kMultiRows, kMultiWaves, true, true>), dim3(multi_gemv_grid(c)),
                            dim3(kMultiWaves * 64), 0, s.stream, a);
@@ -504,6 +567,7 @@ int multi_residual_tail(lam_hip_ctx *c, const void *X, const double *shift, RK r
     ShardBase &s = c->sh[0];
     const int vb = vec_grid(c->n);
     LAMCHK(multi_stage_solution(c, X, K));
+    LAMCHK(pack_many_maybe(c, K));
     LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr, shift)));
     hipLaunchKernelGGL(residual, dim3(vb), dim3(kBlock), 0, s.stream, (const TV *)m.B, (const TV *)m.AP, c->n, m.part_rr, m.part_vec);
     HIPCHK(c, hipGetLastError());
@@ -541,7 +605,12 @@ double multi_gemv_bytes(const lam_hip_ctx *c, int K)
         return (double)c->esz_a() * ((double)c->n * ((double)c->n + 1.0) / 2.0) + (double)c->esz_v() * 2.0 * (double)K * (double)c->n +
                2.0 * (double)c->esz_v() * (double)K *
                    ((double)m.sym.rowpart_elems + (double)m.sym.ntasks * (double)kBlock * (16.0 / (double)c->esz_a()));
-    return (double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)K * (double)c->n;
+    // the image: its elements, headers and max(count, 64) values of every list, each once (what a visit that starts inside a unit
+    // re-reads of its list, header and middle / high bytes is overhead, not counted -- as p, which every workgroup re-reads, is counted once)
+    if (c->packed_many_effective)
+        return (double)c->pack.nrows * (double)c->pack.ntiles * (double)(kPackTileBytes + 4) + 8.0 * (double)c->pack.exc_total +
+               8.0 * 2.0 * (double)K * (double)c->n;
+    return(double)c->esz_a() * (double)c->n * (double)c->n + (double)c->esz_v() * 2.0 * (double)K * (double)c->n;
 }
 
 // what a batched solve reports, CG or MINRES: the per-column arrays and the batch's stats from the scalars' prefix as the host read
@@ -607,6 +676,7 @@ int multi_drive(lam_hip_ctx *c, int max_iters, const TV *in, TV *out, const Mult
             if (d != 0) break;
             multi_harvest(m, slot, timing);
         }
+        LAMCHK(pack_many_maybe(c, K));          // option "packed_many": in front of the product step, outside its event pair
         const double te = now_s();
         const bool timed = timed_iteration(c, s0, k);
         m.timed_slot[slot] = timed;
@@ -709,6 +779,7 @@ int multi_solve(lam_hip_ctx *c, const char *fn, int precond, MultiGuess guess, c
             if (guess == kGuessCurrent) LAMCHK(multi_stage_solution(c, m.X, m.K));
             if (guess == kGuessDeflated) LAMCHK((deflate_start<TV, K>(c)));
             // GUESS: AP = A x0 ((A + s_j I) x0 of a shifted batch) of the guess staged in P, outside the iteration's scalars and partials
+            if (GUESS) LAMCHK(pack_many_maybe(c, K));
             if (GUESS) LAMCHK((multi_launch_gemv<TA, TV, K>(c, (const TV *)m.P, (TV *)m.AP, nullptr, nullptr, shift)));
             // x = 0, r = b, p = b, bb_j = b_j.b_j  (PC: p = dinv o b, rz_j = b_j.(dinv o b_j));  GUESS: x = x0, r = b - A x0, p = r,
             // rr_j = r_j.r_j next to bb_j  (PC: p = dinv o r, rz_j = r_j.(dinv o r_j))
@@ -962,6 +1033,7 @@ int lam_hip_gemv_many(lam_hip_ctx *c, int nrhs, const void *x_host, void *y_host
     const int K = multi_k_for(nrhs);
     m.last_K = K;
     LAMCHK(multi_upload(c, nrhs, K, x_host, m.P));
+    LAMCHK(pack_many_maybe(c, K));
     LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
         using I = decltype(impl);
         return multi_launch_gemv<typename ImplTraits<I>::TA, typename ImplTraits<I>::TV, decltype(kc)::value>(
@@ -984,6 +1056,7 @@ int lam_hip_gemv_many_only(lam_hip_ctx *c, int nrhs, int reps, double *sec_per_p
     m.solved = m.ms.valid = false;
     const int K = multi_k_for(nrhs);
     m.last_K = K;
+    LAMCHK(pack_many_maybe(c, K));
     LAMCHK(multi_dispatch(c, K, [&](auto impl, auto kc) -> int {
         using I = decltype(impl);
         using TA = typename ImplTraits<I>::TA;

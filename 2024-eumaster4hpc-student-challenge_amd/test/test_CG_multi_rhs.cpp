@@ -1,6 +1,6 @@
 // Generate-mode driver of the multi-right-hand-side solve (lam_hip_solve_many): dense tridiag(1,2,1) of -s N rows, -k nrhs
 // right-hand sides, column j constant 2^j, solved together with one pass over the matrix per iteration.
-//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m] [-Y 0|1|2]
+//     test_CG_multi_rhs.out -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J] [-w W] [-T] [-S s0,s1,...] [-M] [-m] [-Y 0|1|2] [-P 0|1]
 //     test_CG_multi_rhs.out -s N -E nev [-W s|l|b] [-i max_steps] [-e tol] [-t f64|f32] [-Y 0|1|2]
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters -D m [-W s|l|b] [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]
 //     test_CG_multi_rhs.out -s N -k nrhs -i max_iters -B [-e rel_error] [-t f64|f32] [-T] [-Y 0|1|2]
@@ -22,6 +22,10 @@
 // -Y 0|1|2: option "symmetric_many" of the solver's context (the batched product reads every pair of the matrix once; tridiag(1,2,1)
 // is symmetric).  After the solve one line on STDERR says which product the last batched launch ran ("symmetric_many_effective"), so
 // the CSV stays as it is; with more than 4 columns the option is not effective and the run proceeds on the general product.
+// -P 0|1: option "packed_many" of the solver's context, with every mode of this driver (the general batched product of up to 4 fp64
+// columns reads the 7-byte image of the matrix; without -P the option keeps its default, automatic).  After the solve one line on
+// STDERR says whether the last batched launch read the image ("packed_many_effective"); the CSV stays as it is.  tridiag(1,2,1) is
+// not packable (its rows are zeros but for three elements), so on this driver's matrix the line reports the plain product.
 // -E nev: the Lanczos eigensolver (lam_hip_eigs) in place of a solve: nev extreme eigenpairs of the matrix, -W s (smallest, the
 // default), l (largest) or b (both ends); -i is max_steps (default min(N, 256)), -e is tol; the start vector is
 // lam_hip_generate_random_rhs(0)'s, convergence is checked every 8 steps.  One CSV line per pair found:
@@ -60,9 +64,15 @@
 
 #include "LAM.hpp"
 
-// -Y: set the option in front of the solve (sym < 0: no -Y, nothing is touched) ...
+static int g_packed_many = -2;          // -P: option "packed_many" (-2: no -P, nothing is touched)
+
+// -Y: set the option in front of the solve (sym < 0: no -Y, nothing is touched) ...  (-P travels with it: the same two places)
 static bool set_symmetric_many(lam_hip_ctx *ctx, int sym)
 {
+    if (g_packed_many != -2 && (ctx == nullptr || lam_hip_set_option(ctx, "packed_many", g_packed_many) != 0)) {
+        fprintf(stderr, "Failed to set option packed_many = %d\n", g_packed_many);
+        return false;
+    }
     if (sym < 0) return true;
     if (ctx != nullptr && lam_hip_set_option(ctx, "symmetric_many", sym) == 0) return true;
     fprintf(stderr, "Failed to set option symmetric_many = %d\n", sym);
@@ -71,6 +81,13 @@ static bool set_symmetric_many(lam_hip_ctx *ctx, int sym)
 // ... and say behind it which product ran
 static void report_symmetric_many(lam_hip_ctx *ctx, int sym)
 {
+    if (g_packed_many != -2 && ctx != nullptr) {
+        int64_t eff = 0, k = 0;
+        lam_hip_get_option(ctx, "packed_many_effective", &eff);
+        lam_hip_get_option(ctx, "multi_rhs_k", &k);
+        fprintf(stderr, "packed_many = %d, packed_many_effective = %lld: K = %lld read %s\n", g_packed_many, (long long)eff, (long long)k,
+                eff ? "the packed image" : "the matrix");
+    }
     if (sym < 0 || ctx == nullptr) return;
     int64_t eff = 0, k = 0;
     lam_hip_get_option(ctx, "symmetric_many_effective", &eff);
@@ -352,10 +369,10 @@ int main(int argc, char **argv)
     bool jacobi = false, true_res = false, mshift = false, minres = false, negative = false;
     int warm = -1;                  // -1: no -w
     int sym = -1;                   // -1: no -Y
-    bool bad_sym = false;
+    bool bad_sym = false, bad_packed = false;
     bool bad_warm = false, bad_shifts = false, k_given = false;
     std::vector<double> shifts;
-    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:E:W:D:BQ:h")) != -1) {
+    while ((opt = getopt(argc, argv, "s:k:i:e:t:Jw:TS:MmY:P:E:W:D:BQ:h")) != -1) {
         switch (opt) {
         case 's': rows = (size_t)atoll(optarg); break;
         case 'k': nrhs = atoi(optarg); k_given = true; break;
@@ -379,12 +396,14 @@ int main(int argc, char **argv)
             else bad_eigs = true;
             break;
         case 'Y': bad_sym = strlen(optarg) != 1 || optarg[0] < '0' || optarg[0] > '2'; sym = optarg[0] - '0'; break;
+        case 'P': bad_packed = strlen(optarg) != 1 || optarg[0] < '0' || optarg[0] > '1'; g_packed_many = optarg[0] - '0'; break;
         default:
             fprintf(stderr, "Usage: %s -s N -k nrhs -i max_iters [-e rel_error] [-t f64|f32] [-J (Jacobi preconditioner)] [-w W (two stages)] "
                     "[-T (true residuals)] [-S s0,s1,... (1..%d shifts >= 0: column j solves (A + s_j I) x = b; sets nrhs)] "
                     "[-M (with -S, up to %d shifts: multi-shift CG on one right-hand side; not with -J, -w)] "
                     "[-m (MINRES in place of CG: -S then takes finite shifts of either sign; not with -J, -w, -M)] "
                     "[-Y 0|1|2 (option symmetric_many: the batched product of up to 4 columns reads every pair of the matrix once)] "
+                    "[-P 0|1 (option packed_many: the general batched product of up to 4 fp64 columns reads the 7-byte image of the matrix)] "
                     "[-E nev (Lanczos eigensolver lam_hip_eigs in place of a solve: nev extreme eigenpairs; -W s|l|b smallest / largest / both, "
                     "-i max_steps up to %d, -e tol; not with -J, -w, -S, -M, -m, -k)] "
                     "[-D m (deflated CG on m = 1..%d Ritz pairs of lam_hip_eigs, -W s|l|b; not with -J, -w, -S, -M, -m, -E)] "
@@ -397,6 +416,10 @@ int main(int argc, char **argv)
     }
     if (bad_sym) {
         fprintf(stderr, "Usage: -Y takes 0 (the general batched product), 1 (the symmetric one where it pays) or 2 (always, up to 4 columns)\n");
+        return 1;
+    }
+    if (bad_packed) {
+        fprintf(stderr, "Usage: -P takes 0 (the batched product reads the matrix) or 1 (the packed image, up to 4 fp64 columns)\n");
         return 1;
     }
     if (q_given) {

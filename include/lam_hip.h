@@ -60,6 +60,8 @@ extern "C" {
  *      Added under version 4 likewise (purely additive): option "packed" and the get-only options "packed_effective", "packed_bytes"
  *      and "packed_pack_ns".  Every result is bit for bit what it was, under every value of the option.  Likewise the testing
  *      options "packed_after" and "packed_min_bytes" (defaults: what the automatic mode did before they existed).
+ *      Added under version 4 likewise (purely additive): option "packed_many" and the get-only option "packed_many_effective".
+ *      Every result is bit for bit what it was, under every value of the option.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_LANCZOS, LAM_HIP_EIG_SMALLEST / _LARGEST / _BOTH, lam_hip_eigs,
  *      lam_hip_get_lanczos, lam_hip_get_eigenvectors, lam_hip_eig_residuals, lam_hip_project_out and lam_hip_tridiag_eigen.
  *      Added under version 4 likewise (purely additive): LAM_HIP_MAX_DEFLATION, lam_hip_set_deflation, lam_hip_set_deflation_eigs,
@@ -254,6 +256,13 @@ int lam_hip_true_residual(lam_hip_ctx *ctx, double *rel_res);
  *     stats.gemv_bytes then reports esz (N (N + 1) / 2 + 2 K N) + 2 esz K (row partials + column partials), the partials being
  *     those of the single symmetric product's plan (one per row of every task + 256 * (16 / esz) per task), written once and read
  *     once; t_gemv brackets both launches;
+ *   - option "packed" does not reach these entry points either; their own switch is option "packed_many", default -1 = automatic.
+ *     Under it the general batched product of K <= 4 fp64 columns -- the loop product of every batched solve (CG, Jacobi, shifts,
+ *     MINRES, deflated, block), the guess's A x0, the multi-shift seed, lam_hip_eigs and its eigen-residuals, lam_hip_lanczos_many,
+ *     lam_hip_set_deflation's A W, lam_hip_true_residual_many, lam_hip_gemv_many and lam_hip_gemv_many_only -- reads the lossless
+ *     7-byte image of the matrix that "packed" reads, in the same single launch and with the same partials.  Every result is bit
+ *     for bit the plain product's, under every value.  K = 8 and "symmetric_many" (which reads half the bytes and wins) are untouched;
+ *     stats.gemv_bytes then reports the image's elements, headers and list values, each once, + 8 * 2 K N for the vectors;
  *   - kernels exist for K = 1, 2, 4 and 8 columns; nrhs runs on the smallest K >= nrhs with zero padding columns that are never
  *     updated (get-only option "multi_rhs_k": the K the last batched call ran, 0 before the first);
  *   - the batch state (vectors, scalars, progress word) is the context's own, allocated at the first batched call and independent of
@@ -831,6 +840,23 @@ int lam_hip_gemv_kernel_name(const lam_hip_ctx *ctx, char *buf, size_t len);
  *                   "packed_bytes" (get): the bytes one product then reads (0 when not effective) -- stats.gemv_bytes and
  *                   lam_hip_gemv_kernel_name ("gemv_packed_kernel<...>") report the same kernel;
  *                   "packed_pack_ns" (get): what the last pack took (0 when not effective).
+ *                   The image belongs to the matrix content: once either reader ("packed", "packed_many") has caused it to be
+ *                   built, each reads it wherever its own option is not 0 and its scope holds.
+ *   "packed_many"   the general batched product (lam_hip_*_many*, lam_hip_solve_mshift's seed, lam_hip_eigs, lam_hip_solve_block,
+ *                   lam_hip_lanczos_many, the deflation set-up) of K <= 4 fp64 columns reads the same image.
+ *                   -1 (default) = automatic: under "packed"'s own rules for the content -- 65 products served, single and batched
+ *                   ones of K <= 4 counted together, 8 GiB of matrix, twice the image free -- and at the K admitted by measurement:
+ *                   K = 1 (0.898 of the plain batched product's time at N = 65536, 0.897 at N = 32768; K = 2: 0.964 and 1.040,
+ *                   K = 4: 1.105 and 1.119, both not admitted); 0 = never; 1 = pack in front of the next batched product and
+ *                   read the image at every K <= 4.  Any other value: LAM_HIP_EINVAL, the value in force stays.  Independent of
+ *                   "packed": "packed" = 0 keeps the single product plain and says nothing about the batch.  Scope: LAM_HIP_F64,
+ *                   one shard, as the batch itself (fp32 contexts accept the option and never engage); where "symmetric_many"
+ *                   engages it wins.  Results are bit for bit those of the plain batched product under every value, so a switch
+ *                   in the middle of a batched solve is invisible; contents that are not packable and refused allocations run
+ *                   the plain kernel, as under "packed".
+ *                   "packed_many_effective" (get): 1 if the last batched product launch read the image, else 0 (before the
+ *                   first batched product, at K = 8, under fp32, where "symmetric_many" engaged, on an unpackable or voided
+ *                   content, after a refused allocation).
  *   "symmetric"     the product reads every pair {A[i][j], A[j][i]} ONCE (A must equal its transpose): half the HBM traffic.
  *                   One shard: the upper triangle; several (exchange 1): cyclic half windows per row, each shard contributes
  *                   a full-length vector to the exchange.  1 = where it pays (from 192 MiB of matrix on), 2 = always, 0
